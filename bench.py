@@ -51,6 +51,29 @@ ALG_FLOP_PER_UNIT = 5.7e8    # 1.0e7 calc_fgk x 57 FP64 ops per (E_
 HBM_PEAK_GBS = 8000.0        # MI355X_MICROARCH.md: HBM3E 8 TB/s
 FP64_VALU_PEAK_TF = 78.6     # MI355X vector FP64; MFMA unusable here
 PROFILE_ROUND = "r04"        # profiles/<round>/ holds the rocprofv3 summaries of this build
+DUMP_MAX_BYTES = 64_000_000  # --dump-outputs: at most this much in all
+
+
+def dump_outputs(dirname: str, arrays: dict) -> dict:
+    """--dump-outputs: what the last timed step computed, each array as <dirname>/<name>.npy in
+    float64 (status words are small integers: exact).  The arrays share their leading axis (one
+    entry per incoming energy); above DUMP_MAX_BYTES in all, every array keeps the same seeded
+    sample of it, whose indices go to sample_rows.npy, so that two builds compare element for element."""
+    d = Path(dirname)
+    d.mkdir(parents=True, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    n = len(next(iter(arrays.values())))
+    row_bytes = sum(v.nbytes for v in arrays.values()) / max(n, 1)
+    room = DUMP_MAX_BYTES - 4096 * (len(arrays) + 1)      # (the .npy headers)
+    sampled = n * row_bytes > room
+    if sampled:
+        keep = int(room // (row_bytes + 8))
+        rows = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+        arrays = {k: v[rows] for k, v in arrays.items()}
+        arrays["sample_rows"] = rows.astype(np.float64)
+    for k, v in arrays.items():
+        np.save(d / f"{k}.npy", v)
+    return {"dir": str(d), "files": {k: list(v.shape) for k, v in arrays.items()}, "sampled": sampled}
 
 
 def make_workload(nein: int, L: int) -> dict:
@@ -346,7 +369,14 @@ def main() -> None:
     ap.add_argument("--library-size", type=int, default=423)
     ap.add_argument("--library-thermal", type=int, default=20)
     ap.add_argument("--library-fissionable", type=int, default=30)
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy "
+                         "(float64, at most 64 MB: a seeded sample of rows above that), to compare builds")
     a = ap.parse_args()
+    if a.steps < 1:
+        raise SystemExit("--steps must be at least 1")
+    if a.dump_outputs and a.workload == "library":
+        raise SystemExit("--dump-outputs: the headline and the secondary workloads only")
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_launch(a))
     if a.workload == "library":
@@ -408,17 +438,23 @@ def main() -> None:
 
     # sanity on the timed result, on EVERY rank: each row's P0 sums to 1, no status bits
     res = out.get()
+    res_status = status.get()
     p0 = res[:, :, 0].sum(axis=1)
-    ok = bool((np.abs(p0 - 1.0) < 1e-12).all()) and int(np.abs(status.get()).sum()) == 0
+    ok = bool((np.abs(p0 - 1.0) < 1e-12).all()) and int(np.abs(res_status).sum()) == 0
     shard_check = None
     if strong:
         # the gathered grid against a ONE-GPU call on a stratified subsample, bit for bit (each
         # output element is produced by exactly one work item: SURVEY 8e's determinism contract)
         parts = R.gather(res.reshape(-1))
+        status_parts = R.gather(res_status.astype(np.float64)) if a.dump_outputs else None
         if rank == 0:
             full = np.zeros((a.nein, G, a.order))
             for r, part in enumerate(parts):
                 full[nd.interleaved_shard(a.nein, world, r)] = np.asarray(part).reshape(-1, G, a.order)
+            if status_parts is not None:
+                res_status = np.zeros(a.nein)
+                for r, part in enumerate(status_parts):
+                    res_status[nd.interleaved_shard(a.nein, world, r)] = np.asarray(part)
             sub = np.unique(np.linspace(0, a.nein - 1, min(a.nein, 96)).astype(np.int64))
             one, _ = ndpp_amd.elastic_leg_batch(p, wl["A"], wl["kT"], 1e300, 0.0, wl["ein"][sub],
                                                 wl["row_lo"][sub], wl["w_hi"][sub], wl["f_tab"], wl["bins"])
@@ -593,6 +629,10 @@ def main() -> None:
                             "inner_integrals_by_walk": sum(s.mu_integrals for s in stats) // a.steps,
                             "kernel_ms_per_step": sum(s.gauss_ms for s in stats) / a.steps},
         }
+        if a.dump_outputs:
+            # the moments and status words of the last timed step: all incoming energies (the shard's
+            # under --emulate-rank), in the order of the workload's grid
+            line["outputs_dumped"] = dump_outputs(a.dump_outputs, {"moments": res, "status": res_status})
         if world == 1 and not a.no_cpu_baseline:
             try:
                 import tempfile

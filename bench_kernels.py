@@ -308,6 +308,9 @@ def main(a) -> None:
                             "frac": fr["weighted_total"]["frac_fp64_valu_peak"], "traffic": None,
                             "note": "algorithmic FP64 operations of the reference (SURVEY 8d) / device time; per "
                                     "family in roofline_by_family"}
+    if a.dump_outputs:
+        from bench import dump_outputs
+        line["outputs_dumped"] = dump_outputs(a.dump_outputs, {"out": out})
     if not a.no_cpu_baseline:
         try:
             r = subprocess.run([sys.executable, str(ROOT / "oracle" / "cpu_baseline.py"),
