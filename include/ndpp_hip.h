@@ -544,6 +544,41 @@ int ndpp_chi_egrid(int n_prompt, const ndpp_chi_spectrum *prompt, int n_delay,
  * renormalised to its original sum_g P0.  Bit-identical to the Fortran.        */
 int ndpp_apply_tol_scatt(int L, int G, int n, double *data, double tol);
 
+/* ---- library validation: the truncated Legendre expansion of stored moments
+ *   f(mu_j) = sum_{l < n_moments} (l + 1/2) P_l(mu_j) a_l
+ * on a caller's mu grid (Python passes numpy.linspace(-1, 1, M), the reference's grid).
+ * P_l are the closed forms of calc_pn (legendre.F90:349-432); every f(mu_j) is computed by
+ * one fixed operation sequence, so results repeat bit for bit and the two entry points agree.
+ * mat / moments keep the Legendre index fastest, row stride L; n_moments <= L truncates
+ * the sum (the reference's `order` argument).  Arguments are checked before the device is
+ * touched (NDPP_EINVAL: L outside 1..NDPP_MAX_ORDER, n_moments outside 1..L, n_mu < 1, a mu
+ * that is not finite or outside [-1, 1], a NULL pointer, cap < 0, sizes whose bytes
+ * overflow); without a device NDPP_EDEVICE. n_ein = 0 is an empty, successful call.       */
+typedef struct ndpp_positivity {
+  long   rows;              /* (E_in, group) rows examined                                  */
+  long   negative;          /* rows with some mu_j where !(f >= 0)  (NaN counts as negative) */
+  double min_value;         /* smallest non-NaN f seen; 0.0 for an all-zero E_in; +inf if none */
+  int    min_ein, min_group;/* 0-based, first row in (iE, g) order attaining min_value
+                               (min_group -1: an all-zero E_in; both -1 if no row)           */
+} ndpp_positivity;
+/* Replaces test_scatt_positivity, src/utils/ndpp_data.py:345-396, for one matrix section
+ * mat[n_ein][G][L].  Rows: for each E_in the groups gmin..gmax, the first and last with
+ * P0 > 0 (the writer's rule, scatt.F90:1181-1198, so a read-back file's own gmin/gmax);
+ * interior rows with P0 <= 0 are checked.  An E_in without P0 > 0 is one zero row: counted,
+ * value 0.0, never negative.  A row is negative when !(f >= 0) at some mu_j.  The offending
+ * rows come out in (iE, g) order: the first `cap` of them in neg_rows[k] = {iE, g} (0-based;
+ * the reference reports g + gmin, a double-counted offset), with the row's smallest non-NaN f
+ * (NaN if every f is NaN) in neg_min[k] and its first mu index in neg_mu[k] (both optional).
+ * summary->negative may exceed cap.                                                       */
+int ndpp_scatt_positivity(int n_ein, int G, int L, const double *mat, int n_moments,
+                          int n_mu, const double *mu, long cap, int *neg_rows /* [cap][2] */,
+                          double *neg_min /* [cap] or NULL */, int *neg_mu /* [cap] or NULL */,
+                          ndpp_positivity *summary);
+/* Replaces expand_scatt, src/utils/ndpp_data.py:305-343: out[n_ein][n_mu] = f of the rows
+ * moments[n_ein][L] (one group's, or condensed, moments per E_in).                        */
+int ndpp_expand_moments(int n_ein, int L, const double *moments, int n_moments,
+                        int n_mu, const double *mu, double *out /* [n_ein][n_mu] */);
+
 #ifdef __cplusplus
 }
 #endif

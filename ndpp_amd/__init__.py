@@ -11,7 +11,8 @@ from .lib import (_check, Params, Stats, NdppError, load, library_path, mu_grid,
                   OutputOptions, FMT_ASCII, FMT_BINARY, FMT_NONE, scatt_ascii, chi_ascii, header_ascii,
                   real_to_str, ascii_array, lib_xml, finish_scatt, nuclide_file,
                   set_device, freegas_rough_rows, mapped_runtimes, profile_reset, profile_get,
-                  ST_NONFINITE, ST_RANGE, ST_ORDER_NOISE)
+                  ST_NONFINITE, ST_RANGE, ST_ORDER_NOISE,
+                  Positivity, scatt_positivity, expand_moments)
 from .scatt import binary_search, elastic_brackets, calc_elastic_grid  # noqa: F401
 
 __version__ = "0.2.0"

@@ -43,6 +43,7 @@ EXPORTS = [
     "ndpp_thin_grid", "ndpp_sab_egrid", "ndpp_chi_egrid", "ndpp_real_to_str", "ndpp_ascii_array",
     "ndpp_scatt_ascii", "ndpp_chi_ascii", "ndpp_header_ascii", "ndpp_lib_xml_header",
     "ndpp_lib_xml_nuclide", "ndpp_lib_xml_closer", "ndpp_finish_scatt", "ndpp_nuclide_file",
+    "ndpp_scatt_positivity", "ndpp_expand_moments",
 ]
 
 
@@ -301,6 +302,15 @@ class OutputOptions(C.Structure):
                 ("print_tol", C.c_double), ("thin_tol", C.c_double)]
 
 
+class Positivity(C.Structure):
+    """ndpp_positivity: the summary of one ndpp_scatt_positivity call."""
+    _fields_ = [("rows", C.c_long), ("negative", C.c_long), ("min_value", C.c_double),
+                ("min_ein", C.c_int), ("min_group", C.c_int)]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 FMT_ASCII, FMT_BINARY, FMT_HDF5, FMT_NONE, FMT_HUMAN = 1, 2, 3, 4, 5
 # per-E_in status bits (include/ndpp_hip.h NDPP_ST_*)
 ST_NONFINITE, ST_RANGE, ST_ORDER_NOISE = 1, 2, 4
@@ -557,6 +567,9 @@ def load(build_if_missing: bool = False, torch_compat: bool | None = None) -> C.
                                    C.c_int, c_double_p, C.c_double, c_int_p, c_double_p, c_double_p]
     lib.ndpp_scatt_library.argtypes = [PP, C.c_int, C.POINTER(AceNuclide), C.c_int, c_double_p, C.c_int,
                                        C.POINTER(ScattResult)]
+    lib.ndpp_scatt_positivity.argtypes = [C.c_int, C.c_int, C.c_int, c_double_p, C.c_int, C.c_int, c_double_p,
+                                          C.c_long, c_int_p, c_double_p, c_int_p, C.POINTER(Positivity)]
+    lib.ndpp_expand_moments.argtypes = [C.c_int, C.c_int, c_double_p, C.c_int, C.c_int, c_double_p, c_double_p]
     lib.ndpp_free_scatt_result.argtypes = [C.POINTER(ScattResult)]
     lib.ndpp_free_scatt_result.restype = None
     _lib = lib
@@ -914,6 +927,43 @@ def group_index(e_bins, ein) -> np.ndarray:
     idx = np.zeros(len(e_bins), dtype=np.int32)
     _check(load().ndpp_group_index(len(e_bins), _dp(e_bins), len(ein), _dp(ein), _ip(idx)))
     return idx
+
+
+def scatt_positivity(mat, n_moments=None, mu_points=21, cap=None):
+    """ndpp_scatt_positivity on one dense section mat[n_ein][G][L] (replaces test_scatt_positivity,
+    src/utils/ndpp_data.py:345-396; the rules are in include/ndpp_hip.h).  n_moments: the first
+    n_moments moments (default L); mu_points: M of the grid linspace(-1, 1, M) (the reference's,
+    ndpp_data.py:367).  cap: offending
+    rows returned at most (default: all).  Returns (Positivity summary, rows (k, 2) int32 of
+    (iE, g), row minima (k,), mu index of each minimum (k,))."""
+    mat = _f64(mat)
+    if mat.ndim != 3:
+        raise ValueError(f"mat must be (n_ein, G, L), got shape {mat.shape}")
+    n, G, L = mat.shape
+    mu = np.linspace(-1.0, 1.0, int(mu_points))
+    nm = L if n_moments is None else int(n_moments)
+    cap = n * G if cap is None else int(cap)
+    k = max(cap, 1)
+    rows, rmin, rmu = np.zeros((k, 2), np.int32), np.zeros(k), np.zeros(k, np.int32)
+    s = Positivity()
+    _check(load().ndpp_scatt_positivity(n, G, L, _dp(mat), nm, len(mu), _dp(mu), cap, _ip(rows), _dp(rmin),
+                                        _ip(rmu), C.byref(s)))
+    m = min(cap, s.negative)
+    return s, rows[:m].copy(), rmin[:m].copy(), rmu[:m].copy()
+
+
+def expand_moments(moments, n_moments=None, mu_points=201):
+    """ndpp_expand_moments (replaces expand_scatt, src/utils/ndpp_data.py:305-343): f[iE][j] =
+    sum_{l < n_moments} (l + 1/2) P_l(mu_j) moments[iE][l] for moments (n_ein, L).  Returns (f, mu)."""
+    mom = _f64(moments)
+    if mom.ndim != 2:
+        raise ValueError(f"moments must be (n_ein, L), got shape {mom.shape}")
+    n, L = mom.shape
+    mu = np.linspace(-1.0, 1.0, int(mu_points))
+    nm = L if n_moments is None else int(n_moments)
+    out = np.zeros((n, len(mu)))
+    _check(load().ndpp_expand_moments(n, L, _dp(mom), nm, len(mu), _dp(mu), _dp(out)))
+    return out, mu
 
 
 def _scatt_struct(result: dict):

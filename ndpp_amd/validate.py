@@ -1,0 +1,238 @@
+"""Validation of NDPP libraries: outgoing-group condensation, Legendre expansion of the stored
+moments, and the positivity check -- the library interface of the reference's user guide
+(docs/source/usersguide/utilities.rst; src/utils/ndpp_data.py:272-396, driven over a library by
+src/utils/validate_library.py), on the GPU (include/ndpp_hip.h: ndpp_expand_moments,
+ndpp_scatt_positivity).
+
+Rules (tests/test_validate.py and tests/test_gpu_validate.py pin them):
+
+* Grid: mu_j = numpy.linspace(-1, 1, M).  M defaults to 21 for `positivity` (as
+  validate_library.py) and to 201 for `expand` (as expand_scatt).
+* f(mu_j) = sum_{l < n_moments} (l + 1/2) P_l(mu_j) a_l.  n_moments defaults to L =
+  scatt_order + 1; a larger value is cut to L (the reference's min(order, scatt_order)).
+* Band: for each E_in the rows g = gmin..gmax, the first and last groups with P0 > 0 -- the
+  writer's rule, so for a file read back these are exactly the file's gmin / gmax.  Interior
+  rows with P0 <= 0 are checked.  An E_in without any P0 > 0 is one zero row: it counts in
+  `rows`, its value is 0.0 and it is never negative; its group is reported as -1 (the reference
+  stores such an E_in as gmin = gmax = -1).
+* Negative means !(f >= 0) at some grid point, so NaN moments are reported and never pass.
+  min_value is the smallest non-NaN f (+inf if there is none).
+
+Deviations from the reference utilities, on purpose:
+
+* test_scatt_positivity reports (iE, g + gmin), which counts the band offset twice; the
+  offending rows here are (iE, g), g the 0-based group.
+* condense_outgoing_scatt sizes its result with an undefined name (Nein); `condense` here
+  returns (NE, L) for the section it is given.
+* validate_library.py calls test_scatt_positivity without its required `dtype`; the CLI here
+  checks every scatter section of every table (elastic, inelastic, nu-inelastic).
+
+CLI: python -m ndpp_amd.validate <dir with ndpp_lib.xml> [--mu-points 21] [--moments N]
+[--json FILE]; exit 0 if every section is positive, 1 if any row is negative, 2 on an input
+error (or when the check cannot run: no device).
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import math
+import sys
+from dataclasses import asdict, dataclass, field
+from pathlib import Path
+
+import numpy as np
+
+from . import lib, reader
+
+SECTIONS = ("elastic", "inelastic", "nuinelastic")
+_RESULT_KEYS = {"elastic": "el_mat", "inelastic": "inel_mat", "nuinelastic": "nuinel_mat"}
+
+
+@dataclass
+class SectionReport:
+    rows: int
+    negative: int
+    min_value: float
+    min_ein: int
+    min_group: int
+    offending: list = field(default_factory=list)     # [(iE, g)] in (iE, g) order, 0-based
+    offending_min: list = field(default_factory=list)  # the row's smallest non-NaN f (NaN if none)
+    offending_mu: list = field(default_factory=list)   # index of that minimum on the mu grid
+
+    @property
+    def positive(self) -> bool:
+        return self.negative == 0
+
+
+@dataclass
+class Report:
+    """positivity() of a table or result: one SectionReport per scatter section present."""
+    sections: dict
+    mu_points: int
+    n_moments: int
+
+    @property
+    def positive(self) -> bool:
+        return all(s.positive for s in self.sections.values())
+
+    @property
+    def min_value(self) -> float:
+        return min((s.min_value for s in self.sections.values()), default=math.inf)
+
+    @property
+    def offending(self) -> dict:
+        return {k: s.offending for k, s in self.sections.items()}
+
+    def as_dict(self) -> dict:
+        return {"positive": self.positive, "min_value": _num(self.min_value), "mu_points": self.mu_points,
+                "n_moments": self.n_moments,
+                "sections": {k: _section_dict(s) for k, s in self.sections.items()}}
+
+
+def _num(x: float):
+    """a float for JSON: nan / inf as strings (json.dumps would write bare NaN / Infinity)"""
+    return x if math.isfinite(x) else str(x)
+
+
+def _section_dict(s: SectionReport) -> dict:
+    d = asdict(s)
+    d["positive"] = s.positive
+    d["min_value"] = _num(s.min_value)
+    d["offending_min"] = [_num(v) for v in s.offending_min]
+    return d
+
+
+def _matrix(section) -> np.ndarray:
+    m = section.mat if isinstance(section, reader.ScattSection) else section
+    m = np.asarray(m, dtype=np.float64)
+    if m.ndim != 3:
+        raise ValueError(f"a scatter section is (NE, G, L), got shape {m.shape}")
+    return m
+
+
+def condense(section, groups=None) -> np.ndarray:
+    """Sum of the selected outgoing groups' moments per E_in, (NE, L) (condense_outgoing_scatt,
+    ndpp_data.py:272-303).  section: reader.ScattSection or a dense (NE, G, L) array; groups:
+    0-based, None for all.  The sum runs over ascending g from 0.0, vectorised over E_in -- the
+    reference's order of operations, so the result equals its loop bit for bit.  Host numpy:
+    O(NE G L), no kernel."""
+    mat = _matrix(section)
+    NE, G, L = mat.shape
+    sel = range(G) if groups is None else sorted({int(g) for g in np.atleast_1d(groups)})
+    for g in sel:
+        if not 0 <= g < G:
+            raise ValueError(f"group {g} outside 0..{G - 1}")
+    out = np.zeros((NE, L))
+    for g in sel:
+        out = out + mat[:, g]
+    return out
+
+
+def expand(moments, mu_points: int = 201, n_moments=None):
+    """f[iE][j] = sum_{l < n_moments} (l + 1/2) P_l(mu_j) moments[iE][l] on mu =
+    linspace(-1, 1, mu_points), on the GPU (expand_scatt, ndpp_data.py:305-343).  moments:
+    (NE, L), e.g. one group's moments or condense()'s.  Returns (f (NE, M), mu)."""
+    mom = np.asarray(moments, dtype=np.float64)
+    nm = None if n_moments is None else min(int(n_moments), mom.shape[1])
+    return lib.expand_moments(mom, n_moments=nm, mu_points=int(mu_points))
+
+
+def _sections_of(obj) -> dict:
+    if isinstance(obj, reader.NdppTable):
+        return {k: getattr(obj, k).mat for k in SECTIONS if getattr(obj, k) is not None}
+    if isinstance(obj, dict):            # lib.scatt_nuclide / lib.finish_scatt result
+        return {k: np.asarray(obj[v]) for k, v in _RESULT_KEYS.items()
+                if obj.get(v) is not None and len(obj[v])}
+    return {"section": _matrix(obj)}
+
+
+def positivity(obj, mu_points: int = 21, n_moments=None) -> Report:
+    """The positivity check (test_scatt_positivity, ndpp_data.py:345-396) on the GPU.
+    obj: reader.NdppTable (elastic, inelastic and nu-inelastic), a result dict of
+    lib.scatt_nuclide / lib.finish_scatt (band found from the dense matrix, as the writer finds
+    it, so a result and its file read back give the same report), or one section
+    (reader.ScattSection or a (NE, G, L) array, reported as "section").  Rules: module docstring.
+    Returns a Report: .positive, .offending {section: [(iE, g)]}, .min_value, .sections."""
+    secs = _sections_of(obj)
+    L = max((m.shape[2] for m in secs.values()), default=0)
+    nm = L if n_moments is None else min(int(n_moments), L)
+    out = {}
+    for name, mat in secs.items():
+        s, rows, rmin, rmu = lib.scatt_positivity(mat, n_moments=min(nm, mat.shape[2]), mu_points=int(mu_points))
+        out[name] = SectionReport(int(s.rows), int(s.negative), float(s.min_value), int(s.min_ein),
+                                  int(s.min_group), [tuple(int(v) for v in r) for r in rows],
+                                  [float(v) for v in rmin], [int(v) for v in rmu])
+    return Report(out, int(mu_points), nm)
+
+
+def read_library(directory) -> list:
+    """[(table attributes, NdppTable)] of every table ndpp_lib.xml lists, read with reader.py
+    (BINARY or ASCII per <filetype>); paths are relative to the directory of ndpp_lib.xml."""
+    d = Path(directory)
+    xml = d / "ndpp_lib.xml" if d.is_dir() else d
+    meta = reader.read_lib_xml(xml.read_bytes())
+    ftype = meta.get("filetype", "binary").lower()
+    if ftype not in ("binary", "ascii"):
+        raise ValueError(f"{xml}: filetype {ftype!r} is neither binary nor ascii")
+    read = reader.read_binary if ftype == "binary" else reader.read_ascii
+    return [(t, read((xml.parent / t["path"]).read_bytes())) for t in meta["tables"]]
+
+
+def _print_report(name: str, t: reader.NdppTable, rep: Report, out) -> None:
+    status = "positive" if rep.positive else "NEGATIVE"
+    print(f"{name}: {status}  (P{t.scatt_order}, {t.groups} groups, {rep.n_moments} moments, "
+          f"{rep.mu_points} mu points)", file=out)
+    for sec, s in rep.sections.items():
+        where = (f" at E_in {s.min_ein + 1}, group {s.min_group + 1}" if s.min_group >= 0 else
+                 (f" at E_in {s.min_ein + 1} (all-zero)" if s.min_ein >= 0 else ""))
+        print(f"  {sec:12s} rows {s.rows:7d}  negative {s.negative:7d}  min {s.min_value: .6e}{where}", file=out)
+        for (iE, g), v, j in list(zip(s.offending, s.offending_min, s.offending_mu))[:10]:
+            print(f"      E_in {iE + 1:6d} ({_ein(t, sec, iE):.6e} MeV)  group {g + 1:4d}  "
+                  f"min {v: .6e} at mu = {np.linspace(-1, 1, rep.mu_points)[j]: .4f}", file=out)
+        if s.negative > 10:
+            print(f"      ... {s.negative - 10} more", file=out)
+
+
+def _ein(t: reader.NdppTable, sec: str, iE: int) -> float:
+    return float(getattr(t, sec).ein[iE])
+
+
+def main(argv=None) -> int:
+    ap = argparse.ArgumentParser(prog="python -m ndpp_amd.validate",
+                                 description="Check every scatter section of an NDPP library for negative "
+                                             "Legendre expansions (exit 0: all positive, 1: negative rows, "
+                                             "2: input error or no device).")
+    ap.add_argument("library", help="directory holding ndpp_lib.xml (or the xml file itself)")
+    ap.add_argument("--mu-points", type=int, default=21, help="points of linspace(-1, 1, M) (default 21)")
+    ap.add_argument("--moments", type=int, default=None, help="moments to sum (default: all, scatt_order + 1)")
+    ap.add_argument("--json", default=None, help="write the full report to this file")
+    a = ap.parse_args(argv)
+    if a.mu_points < 1 or (a.moments is not None and a.moments < 1):
+        print("validate: --mu-points and --moments must be at least 1", file=sys.stderr)
+        return 2
+    try:
+        tables = read_library(a.library)
+    except (OSError, ValueError, KeyError, IndexError) as e:
+        print(f"validate: cannot read the library at {a.library}: {e}", file=sys.stderr)
+        return 2
+    full, bad = {}, []
+    for attrs, t in tables:
+        name = attrs.get("name", t.name)
+        try:
+            rep = positivity(t, mu_points=a.mu_points, n_moments=a.moments)
+        except lib.NdppError as e:
+            print(f"validate: {name}: {e}", file=sys.stderr)
+            return 2
+        _print_report(name, t, rep, sys.stdout)
+        full[name] = dict(rep.as_dict(), path=attrs.get("path"))
+        if not rep.positive:
+            bad.append(name)
+    print(f"{len(tables)} tables, {len(bad)} with negative rows" + (": " + ", ".join(bad) if bad else ""))
+    if a.json:
+        Path(a.json).write_text(json.dumps({"library": str(a.library), "positive": not bad, "tables": full},
+                                           indent=1) + "\n")
+    return 1 if bad else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
