@@ -175,6 +175,74 @@ module ndpp_hip_mod
       integer(c_int) :: rc
     end function ndpp_law9_leg_batch
 
+    ! ---- tabular output (include/ndpp_hip.h): each Legendre twin's arguments plus n_tab after p;
+    ! out is (n_tab, G, n_ein), n_tab lab-cosine bins per group.  p % order must be valid, unused.
+    function ndpp_elastic_tab_batch(p, n_tab, A, kT, freegas_cutoff, Q, n_ein, ein, row_lo, &
+                                    w_hi, n_rows, f_tab, G, e_bins, out, status, stats) &
+        bind(C, name="ndpp_elastic_tab_batch") result(rc)
+      import :: c_int, c_double, c_ptr, ndpp_params
+      type(ndpp_params), intent(in) :: p
+      integer(c_int), value :: n_tab
+      real(c_double), value :: A, kT, freegas_cutoff, Q
+      integer(c_int), value :: n_ein, n_rows, G
+      real(c_double), intent(in) :: ein(*), w_hi(*), f_tab(*), e_bins(*)
+      integer(c_int), intent(in) :: row_lo(*)
+      real(c_double), intent(out) :: out(*)
+      integer(c_int), intent(out) :: status(*)
+      type(c_ptr), value :: stats
+      integer(c_int) :: rc
+    end function ndpp_elastic_tab_batch
+
+    function ndpp_file6_tab_batch(p, n_tab, awr, frame_cm, n_ein, ein, row_lo, n_rows, e_grid, &
+                                  row_ptr, eout, pdf, intt, f, G, e_bins, out, status) &
+        bind(C, name="ndpp_file6_tab_batch") result(rc)
+      import :: c_int, c_double, ndpp_params
+      type(ndpp_params), intent(in) :: p
+      integer(c_int), value :: n_tab
+      real(c_double), value :: awr
+      integer(c_int), value :: frame_cm, n_ein, n_rows, G
+      real(c_double), intent(in) :: ein(*), e_grid(*), eout(*), pdf(*), f(*), e_bins(*)
+      integer(c_int), intent(in) :: row_lo(*), row_ptr(*), intt(*)
+      real(c_double), intent(out) :: out(*)
+      integer(c_int), intent(out) :: status(*)
+      integer(c_int) :: rc
+    end function ndpp_file6_tab_batch
+
+    function ndpp_law9_tab_batch(p, n_tab, n_ein, ein, row_lo, w_hi, n_rows, f_tab, n_edata, edata, &
+                                 G, e_bins, out, status) &
+        bind(C, name="ndpp_law9_tab_batch") result(rc)
+      import :: c_int, c_double, ndpp_params
+      type(ndpp_params), intent(in) :: p
+      integer(c_int), value :: n_tab, n_ein, n_rows, n_edata, G
+      real(c_double), intent(in) :: ein(*), w_hi(*), f_tab(*), edata(*), e_bins(*)
+      integer(c_int), intent(in) :: row_lo(*)
+      real(c_double), intent(out) :: out(*)
+      integer(c_int), intent(out) :: status(*)
+      integer(c_int) :: rc
+    end function ndpp_law9_tab_batch
+
+    ! the whole-nuclide entries take the C structs of include/ndpp_hip.h (ndpp_ace_nuclide,
+    ! ndpp_scatt_result), passed as pointers: hosts that build them call these directly
+    function ndpp_scatt_nuclide_tab(p, n_tab, nuc, n_bins, e_bins, nuscatt, out) &
+        bind(C, name="ndpp_scatt_nuclide_tab") result(rc)
+      import :: c_int, c_double, c_ptr, ndpp_params
+      type(ndpp_params), intent(in) :: p
+      integer(c_int), value :: n_tab, n_bins, nuscatt
+      type(c_ptr), value :: nuc, out
+      real(c_double), intent(in) :: e_bins(*)
+      integer(c_int) :: rc
+    end function ndpp_scatt_nuclide_tab
+
+    function ndpp_scatt_library_tab(p, n_tab, n_nuclides, nuclides, n_bins, e_bins, nuscatt, out) &
+        bind(C, name="ndpp_scatt_library_tab") result(rc)
+      import :: c_int, c_double, c_ptr, ndpp_params
+      type(ndpp_params), intent(in) :: p
+      integer(c_int), value :: n_tab, n_nuclides, n_bins, nuscatt
+      type(c_ptr), value :: nuclides, out
+      real(c_double), intent(in) :: e_bins(*)
+      integer(c_int) :: rc
+    end function ndpp_scatt_library_tab
+
     function ndpp_last_error() bind(C, name="ndpp_last_error") result(msg)
       import :: c_ptr
       type(c_ptr) :: msg
@@ -215,8 +283,9 @@ contains
     end do
   end function ndpp_hip_error
 
+  ! n_tab (optional, > 0): tabular output, order = n_tab lab-cosine bins per group
   subroutine calc_elastic_grid_hip(nuc, mu_out, rxn_data, Ein, order, E_bins, &
-                                   scatt_mat, ierr)
+                                   scatt_mat, ierr, n_tab)
     type(Nuclide), pointer, intent(in)     :: nuc
     real(8), intent(inout)                 :: mu_out(:)   ! unused for Legendre output
     type(ScattData), intent(inout), target :: rxn_data(:)
@@ -225,17 +294,20 @@ contains
     real(8), intent(in)                    :: E_bins(:)
     real(8), allocatable, intent(out)      :: scatt_mat(:,:,:)
     integer, intent(out)                   :: ierr
+    integer, intent(in), optional          :: n_tab
 
     type(ScattData), pointer :: sd
     type(Reaction),  pointer :: rxn
     type(ndpp_params) :: p
-    integer :: groups, NE, irxn, iE, k, nb, iEg, nuc_iE, M
+    integer :: groups, NE, irxn, iE, k, nb, iEg, nuc_iE, M, ntab
     real(8) :: f, sigS
     real(c_double), allocatable :: f_tab(:,:), ein_b(:), w_hi(:), out(:,:,:)
     integer(c_int), allocatable :: row_lo(:), status(:), where_(:)
 
     groups = size(E_bins) - 1
     NE = size(Ein)
+    ntab = 0
+    if (present(n_tab)) ntab = n_tab
     allocate(scatt_mat(order, groups, NE))
     scatt_mat = ZERO
     ierr = 0
@@ -292,10 +364,17 @@ contains
       ! ---- one GPU call for the whole grid (integrate_distro :533-591)
       if (nb > 0) then
         allocate(out(order, groups, nb), status(nb))
-        p = params_from_global(order, M)
-        ierr = ndpp_elastic_leg_batch(p, sd % awr, sd % kT, sd % freegas_cutoff, &
-                 rxn % Q_value, nb, ein_b, row_lo, w_hi, sd % NE, f_tab, groups, &
-                 E_bins, out, status, c_null_ptr)
+        if (ntab > 0) then
+          p = params_from_global(1, M)
+          ierr = ndpp_elastic_tab_batch(p, ntab, sd % awr, sd % kT, sd % freegas_cutoff, &
+                   rxn % Q_value, nb, ein_b, row_lo, w_hi, sd % NE, f_tab, groups, &
+                   E_bins, out, status, c_null_ptr)
+        else
+          p = params_from_global(order, M)
+          ierr = ndpp_elastic_leg_batch(p, sd % awr, sd % kT, sd % freegas_cutoff, &
+                   rxn % Q_value, nb, ein_b, row_lo, w_hi, sd % NE, f_tab, groups, &
+                   E_bins, out, status, c_null_ptr)
+        end if
         if (ierr /= 0) return
         do k = 1, nb
           scatt_mat(:, :, where_(k)) = out(:, :, k)   ! elastic: no sigma scaling (:494-497)
@@ -321,8 +400,9 @@ contains
   ! sigma * p_valid scaling, the reaction sum and the nu-scatter yield weighting
   ! are applied in the reference's order.
   !=============================================================================
+  ! n_tab (optional, > 0): tabular output, order = n_tab lab-cosine bins per group
   subroutine calc_inelastic_grid_hip(nuc, mu_out, rxn_data, Ein, order, E_bins, nuscatt, &
-                                     scatt_mat, nuscatt_mat, ierr)
+                                     scatt_mat, nuscatt_mat, ierr, n_tab)
     type(Nuclide), pointer, intent(in)     :: nuc
     real(8), intent(inout)                 :: mu_out(:)
     type(ScattData), intent(inout), target :: rxn_data(:)
@@ -333,11 +413,12 @@ contains
     real(8), allocatable, intent(out)      :: scatt_mat(:,:,:)
     real(8), allocatable, intent(out)      :: nuscatt_mat(:,:,:)
     integer, intent(out)                   :: ierr
+    integer, intent(in), optional          :: n_tab
 
     type(ScattData), pointer :: sd
     type(Reaction),  pointer :: rxn
     type(ndpp_params) :: p
-    integer :: groups, NE, irxn, iE, k, nb, iEg, nuc_iE, M, j, ntot, kind
+    integer :: groups, NE, irxn, iE, k, nb, iEg, nuc_iE, M, j, ntot, kind, ntab
     real(8) :: f, sigS, p_valid, yield
     real(c_double), allocatable :: ein_b(:), w_hi(:), scale(:), out(:,:,:), f_tab(:,:)
     real(c_double), allocatable :: eout(:), pdf(:), fcols(:,:)
@@ -354,6 +435,8 @@ contains
     end if
     allocate(temp(order, groups))
     ierr = 0
+    ntab = 0
+    if (present(n_tab)) ntab = n_tab
 
     do irxn = 1, size(rxn_data)
       sd => rxn_data(irxn)
@@ -418,16 +501,26 @@ contains
 
       if (nb > 0) then
         allocate(out(order, groups, nb), status(nb))
-        p = params_from_global(order, M)
+        if (ntab > 0) then
+          p = params_from_global(1, M)
+        else
+          p = params_from_global(order, M)
+        end if
         select case (kind)
         case (1, 3)
           allocate(f_tab(M, sd % NE))
           do k = 1, sd % NE
             f_tab(:, k) = sd % distro(k) % data(:, 1)
           end do
-          if (kind == 1) then
+          if (kind == 1 .and. ntab > 0) then
+            ierr = ndpp_elastic_tab_batch(p, ntab, sd % awr, sd % kT, ZERO, rxn % Q_value, nb, &
+                     ein_b, row_lo, w_hi, sd % NE, f_tab, groups, E_bins, out, status, c_null_ptr)
+          else if (kind == 1) then
             ierr = ndpp_elastic_leg_batch(p, sd % awr, sd % kT, ZERO, rxn % Q_value, nb, &
                      ein_b, row_lo, w_hi, sd % NE, f_tab, groups, E_bins, out, status, c_null_ptr)
+          else if (ntab > 0) then
+            ierr = ndpp_law9_tab_batch(p, ntab, nb, ein_b, row_lo, w_hi, sd % NE, f_tab, &
+                     size(sd % edist % data), sd % edist % data, groups, E_bins, out, status)
           else
             ierr = ndpp_law9_leg_batch(p, nb, ein_b, row_lo, w_hi, sd % NE, f_tab, &
                      size(sd % edist % data), sd % edist % data, groups, E_bins, out, status)
@@ -449,9 +542,15 @@ contains
             pdf(j + 1 : row_ptr(k + 1)) = sd % pdfs(k) % data
             fcols(:, j + 1 : row_ptr(k + 1)) = sd % distro(k) % data
           end do
-          ierr = ndpp_file6_leg_batch(p, sd % awr, merge(1, 0, kind == 2), nb, ein_b, row_lo, &
-                   sd % NE, sd % E_grid, row_ptr, eout, pdf, intt, fcols, groups, E_bins, &
-                   out, status)
+          if (ntab > 0) then
+            ierr = ndpp_file6_tab_batch(p, ntab, sd % awr, merge(1, 0, kind == 2), nb, ein_b, &
+                     row_lo, sd % NE, sd % E_grid, row_ptr, eout, pdf, intt, fcols, groups, &
+                     E_bins, out, status)
+          else
+            ierr = ndpp_file6_leg_batch(p, sd % awr, merge(1, 0, kind == 2), nb, ein_b, row_lo, &
+                     sd % NE, sd % E_grid, row_ptr, eout, pdf, intt, fcols, groups, E_bins, &
+                     out, status)
+          end if
           deallocate(row_ptr, intt, eout, pdf, fcols)
         end select
         if (ierr /= 0) return
@@ -793,11 +892,21 @@ contains
     type(Reaction),   pointer :: rxn
     type(ScattData), allocatable, target :: rxn_data(:)
     real(8), allocatable :: mu_out(:)
-    integer :: num_tot_rxn, i_rxn, k, sd_order
+    integer :: num_tot_rxn, i_rxn, k, sd_order, ntab
     real(8) :: inel_thresh, cutoff
 
     ierr = 0
-    if (scatt_type /= SCATT_TYPE_LEGENDRE) then
+    ! Legendre: order + 1 moments; tabular: order = N lab-cosine bins per group, (N, G, NE)
+    ! matrices (ScattData%init stores order + 1 or order, scattdata_header.F90:114-118)
+    if (scatt_type == SCATT_TYPE_TABULAR) then
+      if (order < 1 .or. order > 128) then
+        ierr = -22
+        return
+      end if
+      ntab = order
+    else if (scatt_type == SCATT_TYPE_LEGENDRE) then
+      ntab = 0
+    else
       ierr = -22
       return
     end if
@@ -831,7 +940,7 @@ contains
 
     cutoff = ZERO
     inel_thresh = energy_bins(size(energy_bins))
-    sd_order = order + 1
+    sd_order = merge(order, order + 1, ntab > 0)
     do k = 1, num_tot_rxn
       call convert_distro_hip(rxn_data(k), ierr)
       if (ierr /= 0) return
@@ -851,11 +960,12 @@ contains
 
     allocate(mu_out(mu_bins))
     mu_out = ZERO
-    call calc_elastic_grid_hip(nuc, mu_out, rxn_data, Ein_el, sd_order, energy_bins, el_mat, ierr)
+    call calc_elastic_grid_hip(nuc, mu_out, rxn_data, Ein_el, sd_order, energy_bins, el_mat, ierr, &
+                               ntab)
     if (ierr /= 0) return
     if (allocated(Ein_inel)) then
       call calc_inelastic_grid_hip(nuc, mu_out, rxn_data, Ein_inel, sd_order, energy_bins, nuscatt, &
-                                   inel_mat, nuinel_mat, ierr)
+                                   inel_mat, nuinel_mat, ierr, ntab)
       if (ierr /= 0) return
     end if
     do k = 1, num_tot_rxn

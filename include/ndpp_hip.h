@@ -44,7 +44,15 @@ extern "C" {
                                   3e-10, legendre.F90:46-140).  Those moments are now evaluated in the
                                   reference's operation order and hold the 1e-10 bar up to P10. */
 
+#define NDPP_ST_TAB_UNSETTLED 8 /* tabular free gas: an E' piece of the row did not settle to the
+                                  error test within 128 panels (the finest estimate is kept) */
+
 #define NDPP_MAX_ORDER 11      /* L = scatt_order+1 <= 11 (ndpp.F90:290-301) */
+
+/* <scatt_type> (constants.F90, ndpp.F90:280-287): what a scattering row holds */
+#define NDPP_SCATT_LEGENDRE 0  /* L Legendre moments per (E_in, group)                 */
+#define NDPP_SCATT_TABULAR  1  /* N bins of the lab cosine per (E_in, group)            */
+#define NDPP_MAX_TAB_BINS 128  /* 1 <= N <= 128                                        */
 
 /* Module `global`'s hidden numerics (global.F90:32-59, defaults
  * constants.F90:70-100, set from ndpp.xml at ndpp.F90:355-423) plus the two
@@ -241,6 +249,48 @@ int ndpp_file6_leg_batch(const ndpp_params *p, double awr, int frame_cm, int n_e
  * edata[n_edata] is edist%data: the TAB1 of the nuclear temperature T(E)
  * followed by the restriction energy U.                                       */
 int ndpp_law9_leg_batch(const ndpp_params *p, int n_ein, const double *ein,
+                        const int *row_lo, const double *w_hi, int n_rows,
+                        const double *f_tab, int n_edata, const double *edata,
+                        int G, const double *e_bins, double *out, int *status);
+
+/* ---- tabular scattering output (scatt_type = NDPP_SCATT_TABULAR) ----------------------
+ * The reference's user guide defines <scatt_type>tabular</scatt_type> with <scatt_order> N as
+ * the number of bins in mu; the reference parses it and writes it into the header but never
+ * computes it (integrate_distro's SCATT_TYPE_TABULAR branch is empty).  Definition here:
+ *   - N equal bins of the LAB cosine, edges b_k = -1 + 2k/N (k = 0..N, b_N = 1 exactly),
+ *     1 <= n_tab <= NDPP_MAX_TAB_BINS, anything else NDPP_EINVAL.  (The reference's unused
+ *     mu_out array, scatt.F90:129-134, holds N points; the guide's N bins are followed.)
+ *   - T[iE][g][k] is the P0 integral of the same path over only the part of its domain whose
+ *     lab cosine lies in bin k: same inputs, same blending of the bracketing rows, same
+ *     normalisation, so sum_k T[iE][g][k] = P0[iE][g] (to rounding; free gas: to its
+ *     quadrature tolerance) and T >= 0 wherever the tables are non-negative.
+ *   - out[n_ein][G][N], bin index fastest: the layout of [G][L]; ndpp_scatt_result.L holds N.
+ * Per path:
+ *   file 4 (two-body CM): the exact integral of the piecewise-linear f(w) over the part of
+ *     [wlo, whi] that the exact two-body kinematics map into bin k (R < 1: split at w = -R,
+ *     where the lab cosine turns; the reference's tolab replaces the part w < -R, of width
+ *     1 - R, by a linear stand-in below -1 that no bin could hold);
+ *   file 6 CM / lab, law 9: every panel of the Legendre integrators' lab-cosine grids
+ *     contributes its exact integral clipped to each bin (panels narrower than 1e-14 nothing,
+ *     as there); the E' points, weights and normalisation are those of the Legendre path;
+ *   free gas: the P0 double integral of calc_fgk over E' in the group and mu in
+ *     [mu_lo, mu_hi] of find_FG_mu, split at the bin edges: Gauss-Legendre panels in mu,
+ *     composite Gauss-Legendre in E' refined until every bin of both rows has settled to
+ *     1e-10 of the row's integral over that E' piece plus 1e-13 (the kernel integrates to ~1), normalised to sum_{g,k} T = 1.
+ * Each entry takes the argument list of its Legendre twin plus n_tab after p.             */
+int ndpp_elastic_tab_batch(const ndpp_params *p, int n_tab, double A, double kT,
+                           double freegas_cutoff, double Q, int n_ein,
+                           const double *ein, const int *row_lo,
+                           const double *w_hi, int n_rows, const double *f_tab,
+                           int G, const double *e_bins, double *out,
+                           int *status, ndpp_stats *stats);
+int ndpp_file6_tab_batch(const ndpp_params *p, int n_tab, double awr, int frame_cm, int n_ein,
+                         const double *ein, const int *row_lo, int n_rows,
+                         const double *e_grid, const int *row_ptr,
+                         const double *eout, const double *pdf, const int *intt,
+                         const double *f, int G, const double *e_bins, double *out,
+                         int *status);
+int ndpp_law9_tab_batch(const ndpp_params *p, int n_tab, int n_ein, const double *ein,
                         const int *row_lo, const double *w_hi, int n_rows,
                         const double *f_tab, int n_edata, const double *edata,
                         int G, const double *e_bins, double *out, int *status);
@@ -453,6 +503,17 @@ void ndpp_free_scatt_result(ndpp_scatt_result *r);
  * out[n_nuclides]; on error every result is freed.                                  */
 int  ndpp_scatt_library(const ndpp_params *p, int n_nuclides, const ndpp_ace_nuclide *nuclides,
                         int n_bins, const double *e_bins, int nuscatt, ndpp_scatt_result *out);
+
+/* calc_scatt(..., scatt_type = tabular, ...): the two calls above with N = n_tab lab-cosine
+ * bins per (E_in, group) instead of Legendre moments (see ndpp_elastic_tab_batch); same
+ * incoming grids, same sigma * p_valid weighting and reaction sum, nu-scatter included.
+ * el_mat / inel_mat / nuinel_mat are (N, G, NE); r->L = N.  p->order must be valid but is unused.
+ * ndpp_scatt_library_tab equals n_nuclides ndpp_scatt_nuclide_tab calls bit for bit.     */
+int  ndpp_scatt_nuclide_tab(const ndpp_params *p, int n_tab, const ndpp_ace_nuclide *nuc,
+                            int n_bins, const double *e_bins, int nuscatt, ndpp_scatt_result *out);
+int  ndpp_scatt_library_tab(const ndpp_params *p, int n_tab, int n_nuclides,
+                            const ndpp_ace_nuclide *nuclides, int n_bins, const double *e_bins,
+                            int nuscatt, ndpp_scatt_result *out);
 
 /* ---- wire format, host only ---------------------------------------
  * The byte stream the reference's BINARY writers produce (stream access: raw

@@ -72,6 +72,32 @@ int file6_leg_batch_sink(const ndpp_params* p, double awr, int frame_cm, int n_e
                          const double* eout, const double* pdf, const int* intt, const double* f, int G,
                          const double* e_bins, double* out, int* status, DeviceSink* sink,
                          const double* f_dev = nullptr);
+// file6_leg_batch_sink with n_tab: n_tab > 0 gives the tabular bins of ndpp_file6_tab_batch, n_tab per
+// group; n_tab = 0 the Legendre moments
+int file6_batch_sink(const ndpp_params* p, double awr, int frame_cm, int n_ein, const double* ein,
+                     const int* row_lo, int n_rows, const double* e_grid, const int* row_ptr,
+                     const double* eout, const double* pdf, const int* intt, const double* f, int G,
+                     const double* e_bins, int n_tab, double* out, int* status, DeviceSink* sink,
+                     const double* f_dev = nullptr);
+// tab_kernels.hip: the tabular counterparts of elastic_leg_batch_sink and law9_leg_batch_sink
+int elastic_tab_batch_sink(const ndpp_params* p, double A, double kT, double freegas_cutoff, double Q,
+                           int n_ein, const double* ein, const int* row_lo, const double* w_hi,
+                           int n_rows, const double* f_tab, int G, const double* e_bins, int n_tab,
+                           double* out, int* status, DeviceSink* sink);
+int law9_tab_batch_sink(const ndpp_params* p, int n_ein, const double* ein, const int* row_lo,
+                        const double* w_hi, int n_rows, const double* f_tab, int n_edata,
+                        const double* edata, int G, const double* e_bins, int n_tab, double* out,
+                        int* status, DeviceSink* sink);
+// P0 of one group's row of L entries: the first moment, or (tab) the sum of the bins
+inline double group_p0(const double* m, int L, bool tab) {
+  if (!tab) return m[0];
+  double s = 0.0;
+  for (int k = 0; k < L; ++k) s += m[k];
+  return s;
+}
+// ndpp_scatt_wire, with the gmin / gmax range found on group_p0(.., tab) (wire.hip)
+long scatt_wire(const ndpp_scatt_result* r, int n_bins, const double* e_bins, bool tab, long cap,
+                unsigned char* buf);
 // ndpp_convert_distro that leaves the table where convert_kernel wrote it: *f_dev receives a
 // device array [total_np][mu_bins] (dev_util.h's cached allocator; release with free_converted)
 // for a consumer on the same device, and nothing of it crosses to the host

@@ -230,16 +230,22 @@ extern "C" void ndpp_free_scatt_result(ndpp_scatt_result* r) {
   memset(r, 0, sizeof(*r));
 }
 
+// n_tab = 0: Legendre moments (L = p->order); n_tab > 0: calc_scatt with scatt_type = tabular,
+// n_tab lab-cosine bins per group (the tabular batch calls; no deferred or level batches)
 static int scatt_nuclide_impl(const ndpp_params* p, const ndpp_ace_nuclide* nuc, int n_bins,
                               const double* e_bins, int nuscatt, ndpp_scatt_result* out,
-                              ElasticDefer* defer) {
+                              ElasticDefer* defer, int n_tab = 0) {
   if (!p || !nuc || !e_bins || !out) return fail(NDPP_EINVAL, "NULL argument");
   memset(out, 0, sizeof(*out));
+  if (n_tab < 0 || n_tab > NDPP_MAX_TAB_BINS)
+    return fail(NDPP_EINVAL, "n_tab=%d outside 1..%d", n_tab, NDPP_MAX_TAB_BINS);
+  if (n_tab > 0 && defer)
+    return fail(NDPP_EINVAL, "tabular output has no deferred (mixed-nuclide) elastic batch");
   if (n_bins < 2) return fail(NDPP_EINVAL, "need at least one group");
   if (nuc->n_grid < 2 || !nuc->energy || !nuc->elastic)
     return fail(NDPP_EINVAL, "nuclide energy grid / elastic cross section missing");
   if (nuc->n_reaction < 1 || !nuc->reactions) return fail(NDPP_EINVAL, "nuclide has no reactions");
-  const int G = n_bins - 1, L = p->order, M = p->mu_bins;
+  const int G = n_bins - 1, L = n_tab > 0 ? n_tab : p->order, M = p->mu_bins;
   const double Etop = e_bins[G];
   int rc;
   HostClock hc;
@@ -425,7 +431,7 @@ static int scatt_nuclide_impl(const ndpp_params* p, const ndpp_ace_nuclide* nuc,
     ElasticDefer lvl;
     const char* nlb = getenv("NDPP_HIP_NO_LEVEL_BATCH");
     const bool host_sum = !elastic && !dev_sum;
-    const bool level_batch = host_sum && !(nlb && nlb[0] == '1');
+    const bool level_batch = host_sum && n_tab == 0 && !(nlb && nlb[0] == '1');
     for (const SD& sd : sds) {
       if (!sd.is_init) continue;
       if ((sd.rxn->MT == 2) != elastic) continue;
@@ -534,7 +540,11 @@ static int scatt_nuclide_impl(const ndpp_params* p, const ndpp_ace_nuclide* nuc,
         hc.lap(2);
         continue;
       }
-      if (kind == 1) {
+      if (kind == 1 && n_tab > 0) {
+        rc = elastic_tab_batch_sink(p, nuc->awr, nuc->kT, elastic ? nuc->freegas_cutoff : 0.0, rx.Q_value, nb,
+                                    ein_b.data(), row_lo.data(), w_hi.data(), sd.NE, sd.f.data(), G, e_bins, n_tab,
+                                    res, status.data(), sink);
+      } else if (kind == 1) {
         rc = elastic_leg_batch_sink(p, nuc->awr, nuc->kT, elastic ? nuc->freegas_cutoff : 0.0,
                                     rx.Q_value, nb, ein_b.data(), row_lo.data(), w_hi.data(), sd.NE,
                                     sd.f.data(), G, e_bins, res, status.data(), sink);
@@ -543,13 +553,16 @@ static int scatt_nuclide_impl(const ndpp_params* p, const ndpp_ace_nuclide* nuc,
         for (int k = 0; k < sd.NE; ++k)
           std::copy(sd.f.begin() + (size_t)sd.row_ptr[k] * M, sd.f.begin() + (size_t)(sd.row_ptr[k] + 1) * M,
                     ftab.begin() + (size_t)k * M);
-        rc = law9_leg_batch_sink(p, nb, ein_b.data(), row_lo.data(), w_hi.data(), sd.NE, ftab.data(),
-                                 sd.edist->n_data, sd.edist->data, G, e_bins, res, status.data(), sink);
+        rc = n_tab > 0 ? law9_tab_batch_sink(p, nb, ein_b.data(), row_lo.data(), w_hi.data(), sd.NE, ftab.data(),
+                                             sd.edist->n_data, sd.edist->data, G, e_bins, n_tab, res,
+                                             status.data(), sink)
+                       : law9_leg_batch_sink(p, nb, ein_b.data(), row_lo.data(), w_hi.data(), sd.NE, ftab.data(),
+                                             sd.edist->n_data, sd.edist->data, G, e_bins, res, status.data(), sink);
       } else {
-        rc = file6_leg_batch_sink(p, nuc->awr, kind == 2 ? 1 : 0, nb, ein_b.data(), row_lo.data(), sd.NE,
-                                  sd.e_grid.data(), sd.row_ptr.data(), sd.eout.data(), sd.pdf.data(),
-                                  sd.intt.data(), sd.f.data(), G, e_bins, res, status.data(), sink,
-                                  sd.f_dev.get());
+        rc = file6_batch_sink(p, nuc->awr, kind == 2 ? 1 : 0, nb, ein_b.data(), row_lo.data(), sd.NE,
+                              sd.e_grid.data(), sd.row_ptr.data(), sd.eout.data(), sd.pdf.data(),
+                              sd.intt.data(), sd.f.data(), G, e_bins, n_tab, res, status.data(), sink,
+                              sd.f_dev.get());
       }
       hc.lap(3);
       if (rc) { ndpp_free_scatt_result(out); return rc; }
@@ -646,6 +659,30 @@ extern "C" int ndpp_scatt_library(const ndpp_params* p, int n_nuclides,
     if (rc == NDPP_OK && d.f_tab.size() * sizeof(double) > kFlushBytes) rc = flush();
   }
   if (rc == NDPP_OK) rc = flush();
+  if (rc != NDPP_OK)
+    for (int k = 0; k < n_nuclides; ++k) ndpp_free_scatt_result(&out[k]);
+  return rc;
+}
+
+extern "C" int ndpp_scatt_nuclide_tab(const ndpp_params* p, int n_tab, const ndpp_ace_nuclide* nuc, int n_bins,
+                                      const double* e_bins, int nuscatt, ndpp_scatt_result* out) {
+  if (out) memset(out, 0, sizeof(*out));
+  if (n_tab < 1 || n_tab > NDPP_MAX_TAB_BINS)
+    return fail(NDPP_EINVAL, "n_tab=%d outside 1..%d", n_tab, NDPP_MAX_TAB_BINS);
+  return scatt_nuclide_impl(p, nuc, n_bins, e_bins, nuscatt, out, nullptr, n_tab);
+}
+
+// one nuclide after the other: the tabular elastic grids are not batched across nuclides, so the
+// results are those of ndpp_scatt_nuclide_tab by construction
+extern "C" int ndpp_scatt_library_tab(const ndpp_params* p, int n_tab, int n_nuclides,
+                                      const ndpp_ace_nuclide* nuclides, int n_bins, const double* e_bins,
+                                      int nuscatt, ndpp_scatt_result* out) {
+  if (n_nuclides < 0 || (n_nuclides > 0 && (!nuclides || !out)))
+    return fail(NDPP_EINVAL, "n_nuclides=%d or NULL array", n_nuclides);
+  for (int k = 0; k < n_nuclides; ++k) memset(&out[k], 0, sizeof(out[k]));
+  int rc = NDPP_OK;
+  for (int k = 0; k < n_nuclides && rc == NDPP_OK; ++k)
+    rc = ndpp_scatt_nuclide_tab(p, n_tab, &nuclides[k], n_bins, e_bins, nuscatt, &out[k]);
   if (rc != NDPP_OK)
     for (int k = 0; k < n_nuclides; ++k) ndpp_free_scatt_result(&out[k]);
   return rc;

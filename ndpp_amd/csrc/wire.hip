@@ -29,13 +29,14 @@ struct Writer {
 
 
 // one matrix section of print_scatt_bin: per E_in "gmin, gmax, moments of gmin..gmax",
-// the range found on the P0 moment (:1181-1198); mat is (L, G, n) in Fortran order
-void put_matrix(Writer& w, const double* mat, int n, int G, int L) {
+// the range found on the P0 moment (:1181-1198); mat is (L, G, n) in Fortran order.
+// Tabular rows (tab): the range is found on the group's bin sum, its P0.
+void put_matrix(Writer& w, const double* mat, int n, int G, int L, bool tab) {
   for (int iE = 0; iE < n; ++iE) {
     const double* m = mat + (size_t)iE * G * L;
     int gmin = 1, gmax = G;
-    while (gmin <= G && !(m[(size_t)(gmin - 1) * L] > 0.0)) ++gmin;
-    while (gmax >= 1 && !(m[(size_t)(gmax - 1) * L] > 0.0)) --gmax;
+    while (gmin <= G && !(group_p0(m + (size_t)(gmin - 1) * L, L, tab) > 0.0)) ++gmin;
+    while (gmax >= 1 && !(group_p0(m + (size_t)(gmax - 1) * L, L, tab) > 0.0)) --gmax;
     if (gmin > gmax) {
       w.i32(0); w.i32(0);
     } else {
@@ -64,6 +65,11 @@ extern "C" int ndpp_group_index(int n_bins, const double* e_bins, int n_ein, con
 
 extern "C" long ndpp_scatt_wire(const ndpp_scatt_result* r, int n_bins, const double* e_bins,
                                 long cap, unsigned char* buf) {
+  return ndpp::scatt_wire(r, n_bins, e_bins, false, cap, buf);
+}
+
+long ndpp::scatt_wire(const ndpp_scatt_result* r, int n_bins, const double* e_bins, bool tab, long cap,
+                      unsigned char* buf) {
   if (!r || !e_bins || n_bins != r->G + 1 || r->n_el < 1 || !r->ein_el || !r->el_mat) {
     fail(NDPP_EINVAL, "scatt_wire: incomplete result");
     return -1;
@@ -74,14 +80,14 @@ extern "C" long ndpp_scatt_wire(const ndpp_scatt_result* r, int n_bins, const do
   w.f64s(r->ein_el, r->n_el);
   ndpp_group_index(n_bins, e_bins, r->n_el, r->ein_el, gi.data());
   w.put(gi.data(), 4 * (size_t)n_bins);
-  put_matrix(w, r->el_mat, r->n_el, r->G, r->L);
+  put_matrix(w, r->el_mat, r->n_el, r->G, r->L, tab);
   if (r->n_inel > 0) {
     w.i32(r->n_inel);
     w.f64s(r->ein_inel, r->n_inel);
     ndpp_group_index(n_bins, e_bins, r->n_inel, r->ein_inel, gi.data());
     w.put(gi.data(), 4 * (size_t)n_bins);
-    put_matrix(w, r->inel_mat, r->n_inel, r->G, r->L);
-    if (r->nuinel_mat) put_matrix(w, r->nuinel_mat, r->n_inel, r->G, r->L);
+    put_matrix(w, r->inel_mat, r->n_inel, r->G, r->L, tab);
+    if (r->nuinel_mat) put_matrix(w, r->nuinel_mat, r->n_inel, r->G, r->L, tab);
   } else {
     w.i32(0);
   }

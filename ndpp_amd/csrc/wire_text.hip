@@ -98,13 +98,40 @@ std::string trimmed(const char* c) {
   return s;
 }
 
+// apply_tol_scatt (scatt.F90:786-818) for tabular rows data[n][G][N]: a group's P0 is the sum of
+// its bins; groups with P0 in (0, tol) are zeroed and the row is renormalised to its original
+// total (sums compensated like apply_tol_kernel's)
+void apply_tol_tab(int N, int G, int n, double* data, double tol) {
+  auto total = [&](const double* d) {
+    double s = 0.0, c = 0.0;
+    for (int g = 0; g < G; ++g) {
+      const double y = group_p0(d + (size_t)g * N, N, true) - c, t = s + y;
+      c = (t - s) - y;
+      s = t;
+    }
+    return s;
+  };
+  for (int i = 0; i < n; ++i) {
+    double* d = data + (size_t)i * G * N;
+    const double orig = total(d);
+    for (int g = 0; g < G; ++g) {
+      const double p0 = group_p0(d + (size_t)g * N, N, true);
+      if (p0 > 0.0 && p0 < tol)
+        for (int k = 0; k < N; ++k) d[(size_t)g * N + k] = 0.0;
+    }
+    const double s = total(d);
+    const double norm = (orig > 0.0) ? orig / s : 0.0;
+    for (int k = 0; k < G * N; ++k) d[k] = d[k] * norm;
+  }
+}
+
 // one matrix section of print_scatt_ascii (:923-939)
-void ascii_matrix(std::string& s, const double* mat, int n, int G, int L) {
+void ascii_matrix(std::string& s, const double* mat, int n, int G, int L, bool tab) {
   for (int iE = 0; iE < n; ++iE) {
     const double* m = mat + (size_t)iE * G * L;
     int gmin = 1, gmax = G;
-    while (gmin <= G && !(m[(size_t)(gmin - 1) * L] > 0.0)) ++gmin;
-    while (gmax >= 1 && !(m[(size_t)(gmax - 1) * L] > 0.0)) --gmax;
+    while (gmin <= G && !(group_p0(m + (size_t)(gmin - 1) * L, L, tab) > 0.0)) ++gmin;
+    while (gmax >= 1 && !(group_p0(m + (size_t)(gmax - 1) * L, L, tab) > 0.0)) --gmax;
     if (gmin > gmax) {
       i20(s, 0); i20(s, 0); s += '\n';
     } else {
@@ -123,21 +150,21 @@ bool scatt_ok(const ndpp_scatt_result* r, int n_bins, const double* e_bins) {
   return r && e_bins && n_bins == r->G + 1 && r->n_el >= 1 && r->ein_el && r->el_mat;
 }
 
-std::string scatt_ascii(const ndpp_scatt_result* r, int n_bins, const double* e_bins) {
+std::string scatt_ascii(const ndpp_scatt_result* r, int n_bins, const double* e_bins, bool tab = false) {
   std::string s;
   std::vector<int> gi(n_bins);
   i20(s, r->n_el); s += '\n';
   ascii_array(s, r->ein_el, r->n_el);
   ndpp_group_index(n_bins, e_bins, r->n_el, r->ein_el, gi.data());
   ascii_int_array(s, gi.data(), n_bins);
-  ascii_matrix(s, r->el_mat, r->n_el, r->G, r->L);
+  ascii_matrix(s, r->el_mat, r->n_el, r->G, r->L, tab);
   if (r->n_inel > 0) {
     i20(s, r->n_inel); s += '\n';
     ascii_array(s, r->ein_inel, r->n_inel);
     ndpp_group_index(n_bins, e_bins, r->n_inel, r->ein_inel, gi.data());
     ascii_int_array(s, gi.data(), n_bins);
-    ascii_matrix(s, r->inel_mat, r->n_inel, r->G, r->L);
-    if (r->nuinel_mat) ascii_matrix(s, r->nuinel_mat, r->n_inel, r->G, r->L);
+    ascii_matrix(s, r->inel_mat, r->n_inel, r->G, r->L, tab);
+    if (r->nuinel_mat) ascii_matrix(s, r->nuinel_mat, r->n_inel, r->G, r->L, tab);
   } else {
     i20(s, 0); s += '\n';
   }
@@ -269,11 +296,22 @@ extern "C" int ndpp_finish_scatt(const ndpp_output_options* o, ndpp_scatt_result
                                  const double* e_bins, double* thin_report) {
   if (!o || !scatt_ok(r, n_bins, e_bins)) return fail(NDPP_EINVAL, "finish_scatt: bad argument");
   const int L = r->L, G = r->G;
-  int rc = ndpp_apply_tol_scatt(L, G, r->n_el, r->el_mat, o->print_tol);
+  int rc;
+  if (o->scatt_type == NDPP_SCATT_TABULAR) {
+    // tabular rows: the tolerance rule on each group's bin sum (host side)
+    apply_tol_tab(L, G, r->n_el, r->el_mat, o->print_tol);
+    if (r->n_inel > 0) {
+      apply_tol_tab(L, G, r->n_inel, r->inel_mat, o->print_tol);
+      if (o->nuscatter && r->nuinel_mat) apply_tol_tab(L, G, r->n_inel, r->nuinel_mat, o->print_tol);
+    }
+    rc = NDPP_OK;
+  } else {
+  rc = ndpp_apply_tol_scatt(L, G, r->n_el, r->el_mat, o->print_tol);
   if (rc == NDPP_OK && r->n_inel > 0) {
     rc = ndpp_apply_tol_scatt(L, G, r->n_inel, r->inel_mat, o->print_tol);
     if (rc == NDPP_OK && o->nuscatter && r->nuinel_mat)
       rc = ndpp_apply_tol_scatt(L, G, r->n_inel, r->nuinel_mat, o->print_tol);
+  }
   }
   if (rc != NDPP_OK) return rc;
   double rep[4] = {0, 0, 0, 0};
@@ -303,6 +341,11 @@ extern "C" long ndpp_nuclide_file(const ndpp_output_options* o, const char* name
     fail(NDPP_EINVAL, "nuclide_file: lib_format must be NDPP_FMT_ASCII or NDPP_FMT_BINARY");
     return -1;
   }
+  const bool tab = o->scatt_type == NDPP_SCATT_TABULAR;
+  if (tab && is_sab) {
+    fail(NDPP_EINVAL, "nuclide_file: tabular output of thermal S(alpha,beta) tables is not supported");
+    return -1;
+  }
   const bool with_chi = o->integrate_chi && !is_sab && n_chi > 0;
   if (with_chi && (!e_chi || !chi_t || !chi_p || n_prec < 0 || (n_prec > 0 && !chi_d))) {
     fail(NDPP_EINVAL, "nuclide_file: chi arrays missing");
@@ -317,7 +360,7 @@ extern "C" long ndpp_nuclide_file(const ndpp_output_options* o, const char* name
   if (o->lib_format == NDPP_FMT_ASCII) {
     std::string s = header_ascii(name, name_len, kT, G, e_bins, o->scatt_type, o->scatt_order, nu_int,
                                  chi_int, o->mu_bins, o->thin_tol);
-    s += scatt_ascii(&pr, n_bins, e_bins);
+    s += scatt_ascii(&pr, n_bins, e_bins, tab);
     if (with_chi) s += chi_ascii(G, n_chi, n_prec, e_chi, chi_t, chi_p, chi_d);
     return emit(s, cap, buf);
   }
@@ -334,7 +377,7 @@ extern "C" long ndpp_nuclide_file(const ndpp_output_options* o, const char* name
         return ndpp_header_wire(name, name_len, kT, G, e_bins, o->scatt_type, o->scatt_order, nu_int,
                                 chi_int, o->mu_bins, o->thin_tol, c, b); }))
     return -1;
-  if (!section([&](long c, unsigned char* b) { return ndpp_scatt_wire(&pr, n_bins, e_bins, c, b); }))
+  if (!section([&](long c, unsigned char* b) { return scatt_wire(&pr, n_bins, e_bins, tab, c, b); }))
     return -1;
   if (with_chi && !section([&](long c, unsigned char* b) {
         return ndpp_chi_wire(G, n_chi, n_prec, e_chi, chi_t, chi_p, chi_d, c, b); }))

@@ -44,6 +44,8 @@ EXPORTS = [
     "ndpp_scatt_ascii", "ndpp_chi_ascii", "ndpp_header_ascii", "ndpp_lib_xml_header",
     "ndpp_lib_xml_nuclide", "ndpp_lib_xml_closer", "ndpp_finish_scatt", "ndpp_nuclide_file",
     "ndpp_scatt_positivity", "ndpp_expand_moments",
+    "ndpp_elastic_tab_batch", "ndpp_file6_tab_batch", "ndpp_law9_tab_batch", "ndpp_scatt_nuclide_tab",
+    "ndpp_scatt_library_tab",
 ]
 
 
@@ -313,7 +315,7 @@ class Positivity(C.Structure):
 
 FMT_ASCII, FMT_BINARY, FMT_HDF5, FMT_NONE, FMT_HUMAN = 1, 2, 3, 4, 5
 # per-E_in status bits (include/ndpp_hip.h NDPP_ST_*)
-ST_NONFINITE, ST_RANGE, ST_ORDER_NOISE = 1, 2, 4
+ST_NONFINITE, ST_RANGE, ST_ORDER_NOISE, ST_TAB_UNSETTLED = 1, 2, 4, 8
 
 
 class NdppError(RuntimeError):
@@ -572,6 +574,12 @@ def load(build_if_missing: bool = False, torch_compat: bool | None = None) -> C.
     lib.ndpp_expand_moments.argtypes = [C.c_int, C.c_int, c_double_p, C.c_int, C.c_int, c_double_p, c_double_p]
     lib.ndpp_free_scatt_result.argtypes = [C.POINTER(ScattResult)]
     lib.ndpp_free_scatt_result.restype = None
+    # tabular output: the Legendre twins' argument lists with n_tab after p
+    lib.ndpp_elastic_tab_batch.argtypes = [PP, C.c_int] + lib.ndpp_elastic_leg_batch.argtypes[1:]
+    lib.ndpp_file6_tab_batch.argtypes = [PP, C.c_int] + lib.ndpp_file6_leg_batch.argtypes[1:]
+    lib.ndpp_law9_tab_batch.argtypes = [PP, C.c_int] + lib.ndpp_law9_leg_batch.argtypes[1:]
+    lib.ndpp_scatt_nuclide_tab.argtypes = [PP, C.c_int] + lib.ndpp_scatt_nuclide.argtypes[1:]
+    lib.ndpp_scatt_library_tab.argtypes = [PP, C.c_int] + lib.ndpp_scatt_library.argtypes[1:]
     _lib = lib
     return lib
 
@@ -747,6 +755,58 @@ def law9_leg_batch(params: Params, ein, row_lo, w_hi, f_tab, edata, e_bins):
     return out, status
 
 
+SCATT_LEGENDRE, SCATT_TABULAR, MAX_TAB_BINS = 0, 1, 128
+
+
+def elastic_tab_batch(params: Params, n_tab, A, kT, freegas_cutoff, Q, ein, row_lo, w_hi, f_tab, e_bins):
+    """ndpp_elastic_tab_batch: elastic_leg_batch's P0 split into n_tab lab-cosine bins.
+    Returns out[n_ein][G][n_tab], status[n_ein]."""
+    ein, w_hi, f_tab, e_bins = map(_f64, (ein, w_hi, f_tab, e_bins))
+    row_lo = np.ascontiguousarray(row_lo, dtype=np.int32)
+    n, G = ein.shape[0], e_bins.shape[0] - 1
+    p = Params.from_buffer_copy(params)
+    p.mu_bins = f_tab.shape[1]
+    out = np.zeros((n, G, max(int(n_tab), 0)))
+    status = np.zeros(n, dtype=np.int32)
+    _check(load().ndpp_elastic_tab_batch(
+        C.byref(p), int(n_tab), A, kT, freegas_cutoff, Q, n, _dp(ein), _ip(row_lo), _dp(w_hi),
+        f_tab.shape[0], _dp(f_tab), G, _dp(e_bins), _dp(out), _ip(status), None))
+    return out, status
+
+
+def file6_tab_batch(params: Params, n_tab, awr, frame_cm, ein, row_lo, e_grid, row_ptr, eout, pdf,
+                    intt, f, e_bins):
+    """ndpp_file6_tab_batch: file6_leg_batch's P0 in n_tab lab-cosine bins."""
+    ein, e_grid, eout, pdf, f, e_bins = map(_f64, (ein, e_grid, eout, pdf, f, e_bins))
+    row_lo = np.ascontiguousarray(row_lo, dtype=np.int32)
+    row_ptr = np.ascontiguousarray(row_ptr, dtype=np.int32)
+    intt = np.ascontiguousarray(intt, dtype=np.int32)
+    p = Params.from_buffer_copy(params)
+    p.mu_bins = f.shape[1]
+    G = e_bins.shape[0] - 1
+    out = np.zeros((len(ein), G, max(int(n_tab), 0)))
+    status = np.zeros(len(ein), dtype=np.int32)
+    _check(load().ndpp_file6_tab_batch(C.byref(p), int(n_tab), awr, int(bool(frame_cm)), len(ein), _dp(ein),
+                                       _ip(row_lo), len(e_grid), _dp(e_grid), _ip(row_ptr), _dp(eout),
+                                       _dp(pdf), _ip(intt), _dp(f), G, _dp(e_bins), _dp(out), _ip(status)))
+    return out, status
+
+
+def law9_tab_batch(params: Params, n_tab, ein, row_lo, w_hi, f_tab, edata, e_bins):
+    """ndpp_law9_tab_batch: law9_leg_batch's P0 in n_tab lab-cosine bins."""
+    ein, w_hi, f_tab, edata, e_bins = map(_f64, (ein, w_hi, f_tab, edata, e_bins))
+    row_lo = np.ascontiguousarray(row_lo, dtype=np.int32)
+    p = Params.from_buffer_copy(params)
+    p.mu_bins = f_tab.shape[1]
+    G = e_bins.shape[0] - 1
+    out = np.zeros((len(ein), G, max(int(n_tab), 0)))
+    status = np.zeros(len(ein), dtype=np.int32)
+    _check(load().ndpp_law9_tab_batch(C.byref(p), int(n_tab), len(ein), _dp(ein), _ip(row_lo), _dp(w_hi),
+                                      f_tab.shape[0], _dp(f_tab), len(edata), _dp(edata), G, _dp(e_bins),
+                                      _dp(out), _ip(status)))
+    return out, status
+
+
 def sab_batch(params: Params, table, ein, e_bins, want_parts: bool = False):
     """ndpp_sab_batch: calc_scattsab's Legendre path (scatt.F90:543-596).  table is a
     SabFlat or the dict SabFlat.from_dict takes.  Returns scatt_mat[n_ein][G][L]
@@ -884,6 +944,37 @@ def scatt_nuclide(params: Params, nuclide, e_bins, nuscatt: bool = True):
     finally:
         load().ndpp_free_scatt_result(C.byref(r))
     return out
+
+
+def scatt_nuclide_tab(params: Params, n_tab, nuclide, e_bins, nuscatt: bool = True):
+    """ndpp_scatt_nuclide_tab == calc_scatt with scatt_type = tabular: scatt_nuclide's result
+    dict with n_tab lab-cosine bins per group in place of the moments (el_mat[n][G][n_tab])."""
+    nuc = nuclide if isinstance(nuclide, AceNuclide) else AceNuclide.from_desc(nuclide)
+    e_bins = _f64(e_bins)
+    r = ScattResult()
+    _check(load().ndpp_scatt_nuclide_tab(C.byref(params), int(n_tab), C.byref(nuc), len(e_bins), _dp(e_bins),
+                                         int(bool(nuscatt)), C.byref(r)))
+    try:
+        return _scatt_result_dict(r)
+    finally:
+        load().ndpp_free_scatt_result(C.byref(r))
+
+
+def scatt_library_tab(params: Params, n_tab, nuclides, e_bins, nuscatt: bool = True):
+    """ndpp_scatt_library_tab: scatt_nuclide_tab for a list of nuclides."""
+    nucs = [n if isinstance(n, AceNuclide) else AceNuclide.from_desc(n) for n in nuclides]
+    arr = (AceNuclide * max(len(nucs), 1))()
+    for k, n in enumerate(nucs):
+        C.memmove(C.byref(arr[k]), C.byref(n), C.sizeof(AceNuclide))
+    e_bins = _f64(e_bins)
+    res = (ScattResult * max(len(nucs), 1))()
+    _check(load().ndpp_scatt_library_tab(C.byref(params), int(n_tab), len(nucs), arr, len(e_bins), _dp(e_bins),
+                                         int(bool(nuscatt)), res))
+    try:
+        return [_scatt_result_dict(res[k]) for k in range(len(nucs))]
+    finally:
+        for k in range(len(nucs)):
+            load().ndpp_free_scatt_result(C.byref(res[k]))
 
 
 def elastic_leg_multi(params: Params, A, kT, freegas_cutoff, Q, ein, nuc_of_ein, row_lo, w_hi,

@@ -146,6 +146,33 @@ def _sections_of(obj) -> dict:
     return {"section": _matrix(obj)}
 
 
+def tab_positivity(obj, cap: int = 1000) -> Report:
+    """The positivity check of a TABULAR table (scatt_type 1: N lab-cosine bins per group, no
+    Legendre expansion): on the host, every entry that is < 0 or NaN counts as negative.  obj: a
+    reader.NdppTable, a scatt_nuclide_tab / finish_scatt result dict or one (NE, G, N) section.
+    Every (E_in, group) is a row; a row is offending when any of its bins is; offending_min is
+    its smallest non-NaN bin (NaN if none) and offending_mu that bin's index.  `negative` counts
+    entries.  The Report has the shape of positivity()'s, with n_moments = N and mu_points = 0."""
+    secs = _sections_of(obj)
+    out = {}
+    N = 0
+    for name, mat in secs.items():
+        NE, G, N = mat.shape
+        bad = ~(mat >= 0.0)
+        fin = np.where(np.isnan(mat), np.inf, mat)
+        mn = float(fin.min()) if mat.size else math.inf
+        if mat.size and math.isfinite(mn):
+            iE, g, _ = np.unravel_index(int(np.argmin(fin)), mat.shape)
+        else:
+            iE = g = -1
+        rows_bad = np.argwhere(bad.any(axis=2))[:cap]
+        omin = [float(fin[i, j].min()) if np.isfinite(fin[i, j]).any() else math.nan for i, j in rows_bad]
+        omu = [int(np.argmax(bad[i, j])) for i, j in rows_bad]
+        out[name] = SectionReport(int(NE * G), int(bad.sum()), mn, int(iE), int(g),
+                                  [(int(i), int(j)) for i, j in rows_bad], omin, omu)
+    return Report(out, 0, int(N))
+
+
 def positivity(obj, mu_points: int = 21, n_moments=None) -> Report:
     """The positivity check (test_scatt_positivity, ndpp_data.py:345-396) on the GPU.
     obj: reader.NdppTable (elastic, inelastic and nu-inelastic), a result dict of
@@ -180,6 +207,15 @@ def read_library(directory) -> list:
 
 def _print_report(name: str, t: reader.NdppTable, rep: Report, out) -> None:
     status = "positive" if rep.positive else "NEGATIVE"
+    if t.scatt_type == reader.SCATT_TYPE_TABULAR:
+        print(f"{name}: {status}  (tabular, {t.groups} groups, {rep.n_moments} bins)", file=out)
+        for sec, s in rep.sections.items():
+            where = f" at E_in {s.min_ein + 1}, group {s.min_group + 1}" if s.min_group >= 0 else ""
+            print(f"  {sec:12s} rows {s.rows:7d}  negative {s.negative:7d}  min {s.min_value: .6e}{where}", file=out)
+            for (iE, g), v, k in list(zip(s.offending, s.offending_min, s.offending_mu))[:10]:
+                print(f"      E_in {iE + 1:6d} ({_ein(t, sec, iE):.6e} MeV)  group {g + 1:4d}  "
+                      f"min {v: .6e}, first in bin {k + 1}", file=out)
+        return
     print(f"{name}: {status}  (P{t.scatt_order}, {t.groups} groups, {rep.n_moments} moments, "
           f"{rep.mu_points} mu points)", file=out)
     for sec, s in rep.sections.items():
@@ -219,7 +255,8 @@ def main(argv=None) -> int:
     for attrs, t in tables:
         name = attrs.get("name", t.name)
         try:
-            rep = positivity(t, mu_points=a.mu_points, n_moments=a.moments)
+            rep = (tab_positivity(t) if t.scatt_type == reader.SCATT_TYPE_TABULAR else
+                   positivity(t, mu_points=a.mu_points, n_moments=a.moments))
         except lib.NdppError as e:
             print(f"validate: {name}: {e}", file=sys.stderr)
             return 2
