@@ -56,7 +56,11 @@ extern "C" {
 
 /* Module `global`'s hidden numerics (global.F90:32-59, defaults
  * constants.F90:70-100, set from ndpp.xml at ndpp.F90:355-423) plus the two
- * sizes every kernel needs.  Read-only during a call. */
+ * sizes every kernel needs.  Read-only during a call.  Every batch call refuses
+ * with NDPP_EINVAL: adaptive_mu_its or adaptive_eout_its outside 0..31 (the
+ * level counters and stacks are sized for 32 levels), and a tolerance (sab_threshold,
+ * brent_mu_thresh, adaptive_mu_tol, adaptive_eout_tol) that is negative, NaN or
+ * infinite (the reference reads only values >= 0). */
 typedef struct ndpp_params {
   int    order;              /* L = scatt_order + 1 Legendre moments          */
   int    mu_bins;            /* M, points of the uniform mu grid (2001)       */

@@ -341,6 +341,15 @@ NDPP_HD double simpson(double w, double f0, double f1, double f2) {
 // (freegas.F90:356-409, incl. the Brent searches) and the three kernel values
 // the root Simpson estimate needs (adaptiveSimpsons_mu, :498-503).
 // -----------------------------------------------------------------------------
+// The tunables for which the Gauss stage's parity with the reference has been measured
+// (tools/parity_tail.py at production size): the reference's inner tree may
+// go at least 15 levels deep and its tolerance is no looser than the default 1e-7.  Outside this box
+// the reference stops early (it accepts whatever Simpson value it has at depth adaptive_mu_its)
+// or accepts coarse estimates, neither of which a converged Gauss rule reproduces: the free-gas
+// pipeline walks every inner integral there.
+NDPP_HD bool fg_gauss_box(int mu_its, double mu_tol) {
+  return mu_its >= 15 && mu_tol <= 1.0E-7;
+}
 // Is the inner integral of this pair in the zone the Gauss rule may take (mu_gauss_task below)?
 constexpr unsigned kGaussNear = 0x80u;     // t_gl flag (prep -> Gauss stage): a "near" candidate
 NDPP_HD unsigned fg_gauss_zone(const FgBatch& B, const FgPair& q, double Ein, double Eout) {
@@ -525,6 +534,10 @@ NDPP_HD unsigned mu_gauss_certify(const FgBatch& B, const FgPair& q, const FView
     }
   };
   for (int dep = 0; dep < cert_depth; ++dep) {
+    // the reference's depth limit: it accepts every node of this level, converged or not, and a
+    // converged Gauss value is not what it computes -- the row goes to the walk (fg_gauss_box keeps
+    // such tunables away from this stage; this is the safeguard)
+    if (dep >= B.mu_its) return 0;
     const int nn = 1 << dep;
     const double hd = (b - a) / (double)nn;
     const double w = hd * (1.0 / 12.0);

@@ -423,6 +423,12 @@ int check_params(const ndpp_params* p, int G) {
   if (p->adaptive_mu_its < 0 || p->adaptive_mu_its >= kMaxLevels ||
       p->adaptive_eout_its < 0 || p->adaptive_eout_its >= kMaxLevels)
     return fail(NDPP_EINVAL, "adaptive_*_its must be in 0..%d", kMaxLevels - 1);
+  // (the reference reads only values >= 0 from ndpp.xml; NaN would make every test fail and
+  // Inf every test pass, neither of which the reference can be asked for)
+  const double tols[4] = {p->sab_threshold, p->brent_mu_thresh, p->adaptive_mu_tol, p->adaptive_eout_tol};
+  for (double t : tols)
+    if (!(t >= 0.0 && t <= 1.7976931348623157e308))
+      return fail(NDPP_EINVAL, "tolerances (sab_threshold, brent_mu_thresh, adaptive_*_tol) must be finite and >= 0");
   return NDPP_OK;
 }
 
@@ -692,7 +698,8 @@ int run_batch_d(const ndpp_params* p, double A, double kT, double cutoff, double
   char* const arena = cv.p;
 
   const char* ng = getenv("NDPP_HIP_GAUSS");        // 0: every inner integral by the adaptive walk
-  const bool gauss_on = NDPP_FAST && look_at_tables && !(ng && ng[0] == '0');
+  const bool gauss_on = NDPP_FAST && look_at_tables && !(ng && ng[0] == '0') &&
+                        fg_gauss_box(p->adaptive_mu_its, p->adaptive_mu_tol);
   const char* nsort = getenv("NDPP_HIP_NO_SORT");   // test hook: walk tasks in creation order
   const bool do_sort = !(nsort && nsort[0] == '1');
 

@@ -517,6 +517,146 @@ def thin_goldens(R):
     print(f"thin: elastic {len(g['ein_el'])} -> {len(xe)} points, inelastic {len(g['ein_inel'])} -> {len(xi)}")
 
 
+# ---- free gas (and file 6) at non-default integration tunables ------------------------------
+# (sab_threshold, brent_mu_thresh, adaptive_mu_tol, adaptive_mu_its, adaptive_eout_tol,
+#  adaptive_eout_its, ne_per_grp): ref_set_params' order; ndpp.xml's defaults
+TUN_DEFAULT = (1e-6, 1e-6, 1e-7, 15, 1e-8, 15, 20)
+
+
+def tunable_points():
+    """The grid of tests/test_tunables.py: one tunable (two for mu_tol 0) away from the default.
+    The mu_its values straddle the split walk's depth (4), the sibling stack's LDS levels, the
+    Gauss certification depths (7 and 8), the Gauss stage's box (15) and the deepest tree the
+    product supports (31)."""
+    pts = []
+
+    def at(**kw):
+        t = dict(zip(("sab", "brent", "mu_tol", "mu_its", "eout_tol", "eout_its", "ne"), TUN_DEFAULT))
+        t.update(kw)
+        pts.append(tuple(t[k] for k in ("sab", "brent", "mu_tol", "mu_its", "eout_tol", "eout_its", "ne")))
+
+    for its in (0, 1, 3, 4, 5, 7, 8, 9, 10, 11, 12, 13, 14, 15, 20, 31):
+        at(mu_its=its)
+    at(mu_its=3, mu_tol=0.0)
+    at(mu_tol=1e-5)
+    at(mu_tol=1e-9)
+    for its in (0, 3, 8, 24):
+        at(eout_its=its)
+    at(eout_tol=1e-5)
+    at(eout_tol=1e-10)
+    at(sab=1e-3)
+    at(sab=1e-10)
+    at(brent=1e-3)
+    at(brent=1e-9)
+    return pts
+
+
+def tunables_tables():
+    """The free-gas tables of freegas_tunables.npz: H-1 linear in mu (the product arithmetic and
+    the Gauss stage), U-238 on 16 groups, H-1 curved in mu (the reference-arithmetic route)."""
+    M = 257
+    mu = mu_grid(M)
+    P2 = 1.5 * mu * mu - 0.5
+    bins2 = np.array([0.0, 6.25e-7, 20.0])
+    bins16 = np.concatenate([[0.0], np.logspace(-9, np.log10(20.0), 16)])
+    return M, {
+        "h1": dict(A=0.999167, L=4, bins=bins2, ein=np.array([2.53e-8, 5e-6]),
+                   f_tab=np.stack([np.full(M, 0.5), 0.5 * (1 + 0.1 * mu), 0.5 * (1 + 0.3 * mu)])),
+        "u238": dict(A=236.0058, L=4, bins=bins16, ein=np.array([0.999e-6]),
+                     f_tab=np.stack([np.full(M, 0.5), 0.5 * (1 + 0.05 * mu), 0.5 * (1 + 0.2 * mu)])),
+        "curved": dict(A=0.999167, L=4, bins=bins2, ein=np.array([4e-8]),
+                       f_tab=np.stack([0.5 * (1 + 0.2 * mu + 0.3 * P2), 0.5 * (1 + 0.3 * mu + 0.4 * P2),
+                                       0.5 * (1 + 0.4 * mu + 0.2 * P2)])),
+    }
+
+
+def tunables_goldens(R):
+    """tests/golden/freegas_tunables.npz: integrate_freegas_leg through the reference at every
+    point of tunable_points() on the tables of tunables_tables(), plus file-6 CM and lab at three
+    ne_per_grp.  Keys: p<k>_tun[7] (TUN_DEFAULT's order) and, per table t, p<k>_<t>_{lo,hi,out}
+    (lo / hi: the two bracketing rows, out: their blend); the tables under <t>_*."""
+    M, tables = tunables_tables()
+    mu = mu_grid(M)
+    kT = 2.5301e-8
+    E_grid = np.array([1e-11, 1e-6, 20.0])
+    out = dict(M=M, kT=kT, E_grid=E_grid, tun_default=np.array(TUN_DEFAULT))
+    for t, T in tables.items():
+        T["row_lo"], T["w_hi"] = brackets(E_grid, T["ein"])
+        out.update({f"{t}_{k}": T[k] for k in ("A", "L", "bins", "ein", "f_tab", "row_lo", "w_hi")})
+    pts = tunable_points()
+    out["n_points"] = len(pts)
+    t0 = time.time()
+    try:
+        for k, tun in enumerate(pts):
+            sab, brent, mu_tol, mu_its, eout_tol, eout_its, ne = tun
+            R.ref_set_params(sab, brent, mu_tol, mu_its, eout_tol, eout_its, ne, 10, 50, 30)
+            out[f"p{k}_tun"] = np.array(tun, dtype=np.float64)
+            for t, T in tables.items():
+                G, L = len(T["bins"]) - 1, T["L"]
+                lo = np.zeros((len(T["ein"]), G, L))
+                hi = np.zeros_like(lo)
+                for n, E in enumerate(T["ein"]):
+                    for r, dst in ((T["row_lo"][n], lo), (T["row_lo"][n] + 1, hi)):
+                        f = np.ascontiguousarray(T["f_tab"][r])
+                        R.ref_integrate_freegas_leg(E, T["A"], kT, dp(f), dp(mu), M, dp(T["bins"]),
+                                                    G + 1, L, dp(dst[n]))
+                # integrate_distro blend, scattdata_header.F90:566,:589
+                w = T["w_hi"][:, None, None]
+                out.update({f"p{k}_{t}_lo": lo, f"p{k}_{t}_hi": hi,
+                            f"p{k}_{t}_out": lo * (1.0 - w) + hi * w})
+            print(f"  tunables {k + 1}/{len(pts)} {tun}: {time.time() - t0:.0f}s", flush=True)
+        out.update(file6_tunables(R, M, mu))
+    finally:
+        R.ref_set_params(*TUN_DEFAULT, 10, 50, 30)
+    np.savez_compressed(HERE / "freegas_tunables.npz", **out)
+
+
+F6_NE_PER_GRP = (2, 7, 40)
+
+
+def file6_tunables(R, M, mu):
+    """unitbase + integrate_file6_{cm,lab}_leg (file6_goldens' recipe, its configuration "b":
+    8 groups, P7, a duplicated last E_out) at ne_per_grp 2, 7 and 40: f6_<ne>_{cm,lab}."""
+    sys.path.insert(0, str(HERE.parent))
+    from synth import kalbach_rows
+    pi = C.POINTER(i)
+    R.ref_unitbase.argtypes = [d, i, i, P, P, i, P, d, i, P, P, i, P, d, pi, P, P, pi, P]
+    R.ref_integrate_file6_cm_leg.argtypes = [P, i, i, P, d, d, P, i, P, P, i, i, P]
+    R.ref_integrate_file6_lab_leg.argtypes = [P, i, i, P, P, i, P, P, i, i, P]
+    L, seed = 8, 44
+    bins = np.concatenate([[0.0], np.logspace(-3, np.log10(20.0), 9)])
+    T = kalbach_rows(M, 6, 6, 14, 0.5, 20.0, seed=seed, dup_last=True, intt=2)
+    G = len(bins) - 1
+    ein = np.array([0.9 * T["e_grid"][k] + 0.1 * T["e_grid"][k + 1] for k in range(3)] +
+                   [0.35 * T["e_grid"][k] + 0.65 * T["e_grid"][k + 1] for k in range(3)])
+    row = np.array([0, 1, 2] * 2, dtype=np.int32)
+    res = dict(f6_L=L, f6_seed=seed, f6_bins=bins, f6_ein=ein, f6_row=row,
+               f6_ne=np.array(F6_NE_PER_GRP))
+    arr = np.ascontiguousarray
+    for ne in F6_NE_PER_GRP:
+        R.ref_set_params(*TUN_DEFAULT[:6], ne, 10, 50, 30)
+        cm = np.zeros((len(ein), G, L))
+        lab = np.zeros((len(ein), G, L))
+        for n, (E, k) in enumerate(zip(ein, row)):
+            a0, a1, a2 = T["row_ptr"][k:k + 3]
+            np1, np2 = a1 - a0, a2 - a1
+            e1, p1, f1 = arr(T["eout"][a0:a1]), arr(T["pdf"][a0:a1]), arr(T["f"][a0:a1])
+            e2, p2, f2 = arr(T["eout"][a1:a2]), arr(T["pdf"][a1:a2]), arr(T["f"][a1:a2])
+            nub, it = C.c_int(), C.c_int()
+            Eo, pd, fE = np.zeros(np1 + np2), np.zeros(np1 + np2), np.zeros((np1 + np2, M))
+            R.ref_unitbase(E, M, np1, dp(e1), dp(p1), int(T["intt"][k]), dp(f1), T["e_grid"][k],
+                           np2, dp(e2), dp(p2), int(T["intt"][k + 1]), dp(f2), T["e_grid"][k + 1],
+                           C.byref(nub), dp(Eo), dp(pd), C.byref(it), dp(fE))
+            n_ = nub.value
+            fEc, Eoc, pdc = arr(fE[:n_]), arr(Eo[:n_]), arr(pd[:n_])
+            R.ref_integrate_file6_cm_leg(dp(fEc), M, n_, dp(mu), E, 236.0058, dp(Eoc), it.value,
+                                         dp(pdc), dp(bins), G + 1, L, dp(cm[n]))
+            R.ref_integrate_file6_lab_leg(dp(fEc), M, n_, dp(mu), dp(Eoc), it.value, dp(pdc),
+                                          dp(bins), G + 1, L, dp(lab[n]))
+        res[f"f6_{ne}_cm"], res[f"f6_{ne}_lab"] = cm, lab
+    return res
+
+
 def main():
     if not REF.exists():
         sys.exit(f"{REF} missing: run `make -C oracle ref` first")
@@ -613,6 +753,8 @@ if __name__ == "__main__":
         library_goldens(load_ref())
     elif len(sys.argv) > 1 and sys.argv[1] == "library":
         library_goldens(load_ref())
+    elif len(sys.argv) > 1 and sys.argv[1] == "tunables":
+        tunables_goldens(load_ref())
     else:
         main()
         grid_goldens(load_ref())
@@ -622,3 +764,4 @@ if __name__ == "__main__":
         text_goldens(load_ref())
         u238_goldens(load_ref())
         library_goldens(load_ref())
+        tunables_goldens(load_ref())

@@ -127,7 +127,8 @@ extern "C" int hostsim_freegas_jobs(const ndpp_params* p, double A, double kT,
   // HOSTSIM_GAUSS=1 (product arithmetic only): the Gauss-rule stage as the device pipeline runs it
   // on tables that are linear in mu
   std::vector<unsigned char> tgl(B.tcap, 0);
-  if (NDPP_FAST && getenv("HOSTSIM_GAUSS") && getenv("HOSTSIM_GAUSS")[0] == '1') {
+  if (NDPP_FAST && getenv("HOSTSIM_GAUSS") && getenv("HOSTSIM_GAUSS")[0] == '1' &&
+      fg_gauss_box(B.mu_its, B.mu_tol)) {     // (ndpp_hip.hip's gate)
     B.t_gl = tgl.data();
     // (the knobs of ndpp_hip.hip's NDPP_HIP_GAUSS_*)
     if (const char* e = getenv("HOSTSIM_GAUSS_RATIO")) B.gl_ratio = atof(e);
