@@ -1,0 +1,420 @@
+"""Standalone driver: `python -m ndpp_amd.run <dir> [--json FILE]` reads <dir>/ndpp.xml, the
+cross_sections.xml it names and the ACE tables listed there, and writes the NDPP library --
+one `<name><library_name>` file per table (default library_name `.g<G>`) and ndpp_lib.xml --
+into <dir>, under the names and in the formats the reference's `ndpp <dir>` writes.
+
+Every step goes through the C ABI (include/ndpp_hip.h):
+  neutron tables   all in ONE scatt_library (scatt_library_tab for scatt_type tabular) call;
+  chi              chi_egrid_lib + chi_batch per fissionable table (integrate_chi);
+  thermal tables   sab_egrid_lib (+ the extra top point) + sab_batch;
+  every table      finish_scatt (print_tol, thinning when thinning_tol > 0), nuclide_file;
+  the run          lib_xml.
+ndpp.xml is read with the reference's defaults (constants.F90) and refusals (ndpp.F90
+init_ndpp); `threads` is accepted and ignored; output_format hdf5 and human are refused (the
+library writes neither); tabular output of a thermal table is refused before anything is
+computed (ndpp_nuclide_file does not write it).
+
+Exit status: 0 library written, 2 input error (nothing written), 3 library or device error
+(nothing written).  Files are written under temporary names and renamed once every table is
+done, so a failed run leaves no partial library.
+--json FILE: one record per table (kind, incoming energies, wall time, device time)."""
+from __future__ import annotations
+
+import argparse
+import json
+import math
+import os
+import sys
+import time
+import xml.etree.ElementTree as ET
+from pathlib import Path
+
+import numpy as np
+
+from . import ace, grid, lib
+
+EXIT_OK, EXIT_INPUT, EXIT_LIBRARY = 0, 2, 3
+
+# constants.F90 defaults of the reference
+DEFAULTS = dict(scatt_type="legendre", scatt_order=5, nuscatter=False, integrate_chi=True, mu_bins=2001,
+                output_format="binary", thinning_tol=0.0, print_tol=1.0e-8, freegas_cutoff=400.0,
+                sab_threshold=1.0e-6, brent_mu_thresh=1.0e-6, adaptive_mu_tol=1.0e-7, adaptive_eout_tol=1.0e-8,
+                adaptive_mu_its=15, adaptive_eout_its=15, sab_epts_per_bin=10, ne_per_grp=20, extend_pts=50,
+                inel_extend_pts=30)
+MAX_LEGENDRE_ORDER = 10
+GLOBAL_FREEGAS_CUTOFF, INFINITE_FREEGAS_CUTOFF = -2.0, -1.0
+_REALS = ("thinning_tol", "print_tol", "freegas_cutoff", "sab_threshold", "brent_mu_thresh", "adaptive_mu_tol",
+          "adaptive_eout_tol")
+_INTS = ("scatt_order", "mu_bins", "threads", "adaptive_mu_its", "adaptive_eout_its", "sab_epts_per_bin",
+         "ne_per_grp", "extend_pts", "inel_extend_pts")
+
+
+class InputError(ValueError):
+    """An input the reference refuses (or this library cannot honour): exit status 2."""
+
+
+def _warn(msg: str) -> None:
+    print(f"ndpp_amd.run: warning: {msg}", file=sys.stderr)
+
+
+def _text(root, tag):
+    el = root.find(tag)
+    return None if el is None or el.text is None else el.text.strip()
+
+
+def _num(root, tag, kind):
+    s = _text(root, tag)
+    if s is None or s == "":
+        return None
+    try:
+        v = kind(s.replace("D", "E").replace("d", "e")) if kind is float else int(s)
+    except ValueError:
+        raise InputError(f"ndpp.xml: <{tag}> {s!r} is not {'a number' if kind is float else 'an integer'}") from None
+    if kind is float and not math.isfinite(v):
+        raise InputError(f"ndpp.xml: <{tag}> must be finite")
+    return v
+
+
+def _parse_xml(path: Path, what: str):
+    try:
+        return ET.parse(path).getroot()
+    except FileNotFoundError:
+        raise InputError(f"{what} '{path}' does not exist!") from None
+    except (ET.ParseError, OSError) as e:
+        raise InputError(f"{what} '{path}': {e}") from None
+
+
+def read_ndpp_xml(run_dir) -> dict:
+    """The run settings of <run_dir>/ndpp.xml (see the module docstring)."""
+    run_dir = Path(run_dir)
+    root = _parse_xml(run_dir / "ndpp.xml", "Data Pre-Processing XML file")
+    s = dict(DEFAULTS)
+    for k in _REALS:
+        v = _num(root, k, float)
+        if v is not None:
+            s[k] = v
+    for k in _INTS:
+        v = _num(root, k, int)
+        if v is not None:
+            s[k] = v
+    xs = _text(root, "cross_sections") or os.environ.get("CROSS_SECTIONS", "").strip()
+    if not xs:
+        raise InputError("No cross_sections.xml file was specified in ndpp.xml or in the CROSS_SECTIONS "
+                         "environment variable.")
+    s["cross_sections"] = str(run_dir / xs) if not os.path.isabs(xs) else xs
+    for k in ("integrate_chi", "nuscatter"):
+        w = (_text(root, k) or "").lower()
+        if w in ("true", "false"):
+            s[k] = w == "true"
+        elif w:
+            _warn(f"Value for <{k}> provided, but does not match TRUE or FALSE. Using default of "
+                  f"{str(DEFAULTS[k]).upper()}.")
+    eb = _text(root, "energy_bins")
+    if not eb:
+        raise InputError("No energy group structure was specified in ndpp.xml.")
+    try:
+        bins = np.array([float(v.replace("D", "E").replace("d", "e")) for v in eb.split()], dtype=np.float64)
+    except ValueError:
+        raise InputError("Invalid energy group structure specified in ndpp.xml; not a list of numbers.") from None
+    if len(bins) < 2 or not np.isfinite(bins).all():
+        raise InputError("Invalid energy group structure specified in ndpp.xml; need at least two finite edges.")
+    if (bins[:-1] < 0).any():
+        raise InputError("Invalid energy group structure specified in ndpp.xml; Groups boundaries be positive.")
+    if (bins[:-1] >= bins[1:]).any():
+        raise InputError("Invalid energy group structure specified in ndpp.xml; Group boundaries must be in "
+                         "increasing order.")
+    if bins[0] != 0.0:
+        raise InputError("Invalid Lower Energy Boundary: Bottom of Lowest Group  Must be Zero!")
+    s["energy_bins"] = bins
+    fmt = (_text(root, "output_format") or "binary").lower()
+    if fmt in ("hdf5", "human"):
+        raise InputError(f"<output_format> {fmt} is not supported: this library writes ascii, binary or none.")
+    if fmt not in ("ascii", "binary", "none"):
+        _warn("Value for <output_format> provided, but does not match ASCII, BINARY, HDF5, HUMAN, or NONE. "
+              "Using default of BINARY.")
+        fmt = "binary"
+    s["output_format"] = fmt
+    s["lib_format"] = {"ascii": lib.FMT_ASCII, "binary": lib.FMT_BINARY, "none": lib.FMT_NONE}[fmt]
+    G = len(bins) - 1
+    s["library_name"] = _text(root, "library_name") or f".g{G}"
+    st = (_text(root, "scatt_type") or "legendre").lower()
+    if st not in ("legendre", "tabular"):
+        _warn(f"Value for <scatt_type> {st!r} does not match LEGENDRE or TABULAR. Using default of LEGENDRE.")
+        st = "legendre"
+    s["scatt_type"] = st
+    n = s["scatt_order"]
+    if n <= 0 or (st == "legendre" and n > MAX_LEGENDRE_ORDER):
+        raise InputError("Invalid negative or zero scatt_order value specified in ndpp.xml." +
+                         (f" (Legendre orders go up to {MAX_LEGENDRE_ORDER})" if n > 0 else ""))
+    if st == "tabular" and n > lib.MAX_TAB_BINS:
+        raise InputError(f"<scatt_order> {n}: tabular output holds at most {lib.MAX_TAB_BINS} bins.")
+    fc = s["freegas_cutoff"]
+    if fc == INFINITE_FREEGAS_CUTOFF:
+        s["freegas_cutoff"] = math.inf
+    elif fc < 0:
+        raise InputError("Invalid negative value of <freegas_cutoff> specified in ndpp.xml. Specify -1 if no "
+                         "cutoff is desired; all other values are invalid.")
+    if s["thinning_tol"] < 0:
+        _warn("Invalid thinning tolerance provided, setting to default of no thinning.")
+        s["thinning_tol"] = 0.0
+    s["thin_tol"] = 0.01 * s["thinning_tol"]                 # percent -> fraction
+    if s["print_tol"] <= 0:
+        _warn("Invalid printing tolerance provided, setting to default.")
+        s["print_tol"] = DEFAULTS["print_tol"]
+    if s["mu_bins"] <= 1:
+        raise InputError("Invalid mu_bins value specified in ndpp.xml. Mu_bins must be two or greater.")
+    for k in ("sab_threshold", "brent_mu_thresh", "adaptive_mu_tol", "adaptive_eout_tol", "sab_epts_per_bin",
+              "ne_per_grp", "extend_pts", "inel_extend_pts", "adaptive_mu_its", "adaptive_eout_its"):
+        if s[k] < 0:
+            raise InputError(f"Invalid <{k}> value specified in ndpp.xml; value must be positive.")
+    for k in ("adaptive_mu_its", "adaptive_eout_its"):
+        if s[k] > 31:
+            raise InputError(f"Invalid <{k}> value {s[k]} specified in ndpp.xml; the library takes 0..31.")
+    return s
+
+
+def read_cross_sections(path) -> dict:
+    """cross_sections.xml: directory (default: the file's own), filetype, record_length, entries,
+    and the ace_table listings with their attributes (freegas_cutoff in kT: -2 = the ndpp.xml
+    value, -1 = no cutoff)."""
+    path = Path(path)
+    root = _parse_xml(path, "Cross sections XML file")
+    directory = _text(root, "directory") or str(path.parent)
+    ft = (_text(root, "filetype") or "ascii")
+    if ft not in ("ascii", "binary"):
+        raise InputError(f"Unknown filetype in cross_sections.xml: {ft}")
+    try:
+        recl, entries = int(_text(root, "record_length") or 0), int(_text(root, "entries") or 0)
+    except ValueError:
+        raise InputError("cross_sections.xml: <record_length> and <entries> must be integers") from None
+    els = root.findall("ace_table")
+    if not els:
+        raise InputError("No ACE table listings present in cross_sections.xml file!")
+    out = []
+    for el in els:
+        a = el.attrib
+        name = a.get("name", "").strip()
+        try:
+            lst = dict(name=name, alias=a.get("alias", "").strip(), zaid=int(a.get("zaid", 0)),
+                       metastable=int(a.get("metastable", 0)) != 0, awr=float(a.get("awr", 0.0)),
+                       kT=float(a.get("temperature", 0.0)), location=int(a.get("location", 0)),
+                       freegas_cutoff=float(a.get("freegas_cutoff", GLOBAL_FREEGAS_CUTOFF)))
+        except ValueError as e:
+            raise InputError(f"cross_sections.xml: ace_table {name!r}: {e}") from None
+        fc = lst["freegas_cutoff"]
+        if fc < 0 and fc not in (INFINITE_FREEGAS_CUTOFF, GLOBAL_FREEGAS_CUTOFF):
+            raise InputError("Invalid value of freegas_cutoff element in cross_sections.xml file!")
+        p = a.get("path", "").strip()
+        lst["path"] = p if p.startswith("/") else os.path.join(directory, p)
+        lst["type"] = "neutron" if name.endswith("c") else "thermal" if name.endswith("t") else "other"
+        out.append(lst)
+    return dict(directory=directory, filetype=ft, record_length=recl, entries=entries, listings=out)
+
+
+def params_of(s: dict) -> lib.Params:
+    order = s["scatt_order"] + 1 if s["scatt_type"] == "legendre" else 1     # tabular: unused, valid
+    p = lib.Params.default(order, s["mu_bins"])
+    for k in ("sab_threshold", "brent_mu_thresh", "adaptive_mu_tol", "adaptive_eout_tol", "adaptive_mu_its",
+              "adaptive_eout_its", "ne_per_grp", "sab_epts_per_bin", "extend_pts", "inel_extend_pts"):
+        setattr(p, k, s[k])
+    return p
+
+
+def options_of(s: dict) -> lib.OutputOptions:
+    return lib.OutputOptions(lib_format=s["lib_format"], scatt_type=int(s["scatt_type"] == "tabular"),
+                             scatt_order=s["scatt_order"], nuscatter=int(s["nuscatter"]),
+                             integrate_chi=int(s["integrate_chi"]), mu_bins=s["mu_bins"], print_tol=s["print_tol"],
+                             thin_tol=s["thin_tol"])
+
+
+def load_tables(s: dict, xs: dict) -> list:
+    """Read every listed table.  Returns [dict(listing, kind, data, file)] in listing order
+    (tables that are neither neutron nor thermal are skipped, as the reference does)."""
+    out = []
+    for lst in xs["listings"]:
+        if lst["type"] == "other":
+            _warn(f"Invalid Entry in cross_sections listings: {lst['name']!r}. NDPP does not support dosimetry "
+                  "Tables! Entry will be ignored.")
+            continue
+        try:
+            t = ace.read_table(lst["path"], lst["location"], xs["filetype"], xs["record_length"], xs["entries"],
+                               expect_name=lst["name"])
+            data = ace.neutron(t) if lst["type"] == "neutron" else ace.thermal(t)
+        except OSError as e:
+            raise InputError(f"ACE library '{lst['path']}' ({lst['name']}): {e.strerror or e}") from None
+        except ValueError as e:
+            raise InputError(str(e)) from None
+        base = t.name.strip() + s["library_name"].strip()
+        if lst["type"] == "neutron":
+            fc = lst["freegas_cutoff"]
+            if fc == GLOBAL_FREEGAS_CUTOFF:
+                fc = s["freegas_cutoff"]
+            data["freegas_cutoff"] = math.inf if fc in (math.inf, INFINITE_FREEGAS_CUTOFF) else fc * data["kT"]
+        else:
+            i = base.find("/")                              # u/o2.10t -> u-o2.10t
+            if i > 0:
+                base = base[:i] + "-" + base[i + 1:]
+        out.append(dict(listing=lst, kind=lst["type"], data=data, file=base))
+    return out
+
+
+def _device_ms() -> float:
+    return float(sum(lib.profile_get().values()))
+
+
+def compute(s: dict, tables: list) -> tuple:
+    """Every table's file bytes and its timing record: ([(file name, bytes)], [record])."""
+    p, o, bins = params_of(s), options_of(s), s["energy_bins"]
+    tab = s["scatt_type"] == "tabular"
+    files, recs = [None] * len(tables), [None] * len(tables)
+    neut = [k for k, t in enumerate(tables) if t["kind"] == "neutron"]
+    if neut:
+        lib.profile_reset()
+        t0 = time.perf_counter()
+        nucs = [tables[k]["data"] for k in neut]
+        res = (lib.scatt_library_tab(p, s["scatt_order"], nucs, bins, s["nuscatter"]) if tab else
+               lib.scatt_library(p, nucs, bins, s["nuscatter"]))
+        wall, dev, last = time.perf_counter() - t0, _device_ms(), float(lib.load().ndpp_last_gpu_ms())
+        call = "scatt_library_tab" if tab else "scatt_library"
+        for k, r in zip(neut, res):
+            t = tables[k]
+            chi, chi_rec = None, None
+            if s["integrate_chi"] and t["data"]["fissionable"]:
+                lib.profile_reset()
+                c0 = time.perf_counter()
+                case = ace.chi_case(t["data"])
+                e_chi = lib.chi_egrid_lib(case)
+                ct, cp, cd = lib.chi_batch(case, bins, e_chi)
+                chi = (e_chi, ct, cp, cd)
+                chi_rec = dict(energies=len(e_chi), wall_s=time.perf_counter() - c0, device_ms=_device_ms(),
+                               last_gpu_ms=float(lib.load().ndpp_last_gpu_ms()))
+            fin, _ = lib.finish_scatt(o, r, bins)
+            if s["lib_format"] != lib.FMT_NONE:
+                files[k] = lib.nuclide_file(o, t["data"]["name"], t["data"]["kT"], fin, bins, chi=chi)
+            recs[k] = dict(name=t["listing"]["name"], kind="neutron", file=t["file"],
+                           energies=dict(elastic=len(r["ein_el"]),
+                                         inelastic=0 if r["ein_inel"] is None else len(r["ein_inel"])),
+                           batch=dict(call=call, tables=len(neut), wall_s=wall, device_ms=dev, last_gpu_ms=last),
+                           chi=chi_rec)
+    for k, t in enumerate(tables):
+        if t["kind"] != "thermal":
+            continue
+        d = t["data"]
+        lib.profile_reset()
+        t0 = time.perf_counter()
+        ein = grid.add_one_more_point(lib.sab_egrid_lib(p, d, bins))
+        mat = lib.sab_batch(p, d, ein, bins)
+        wall, dev, last = time.perf_counter() - t0, _device_ms(), float(lib.load().ndpp_last_gpu_ms())
+        fin, _ = lib.finish_scatt(o, dict(ein_el=ein, el_mat=mat, ein_inel=None, inel_mat=None, nuinel_mat=None),
+                                  bins)
+        if s["lib_format"] != lib.FMT_NONE:
+            files[k] = lib.nuclide_file(o, d["name"], d["kT"], fin, bins, is_sab=True)
+        recs[k] = dict(name=t["listing"]["name"], kind="thermal", file=t["file"],
+                       energies=dict(elastic=len(ein), inelastic=0), wall_s=wall, device_ms=dev, last_gpu_ms=last)
+    return [(t["file"], f) for t, f in zip(tables, files)], recs
+
+
+def lib_xml_of(s: dict, run_dir, tables: list) -> bytes:
+    rows = []
+    for t in tables:
+        lst, d = t["listing"], t["data"]
+        thermal = t["kind"] == "thermal"
+        rows.append(dict(alias=lst["name"] if thermal else lst["alias"], awr=lst["awr"], name=lst["name"],
+                         path=t["file"], kT=lst["kT"], zaid=lst["zaid"], metastable=lst["metastable"],
+                         freegas_cutoff=lst["freegas_cutoff"] if thermal else d["freegas_cutoff"]))
+    return lib.lib_xml(str(Path(run_dir).resolve()) + "/", s["lib_format"], rows, s["energy_bins"],
+                       int(s["scatt_type"] == "tabular"), s["scatt_order"], s["mu_bins"], s["nuscatter"],
+                       s["integrate_chi"], s["print_tol"], s["thin_tol"])
+
+
+def _refuse_thermal_tabular(s: dict, tables: list) -> None:
+    """scatt_type tabular with a thermal table: the writer's refusal, before any device work."""
+    if s["scatt_type"] != "tabular" or s["lib_format"] == lib.FMT_NONE:
+        return
+    th = [t for t in tables if t["kind"] == "thermal"]
+    if not th:
+        return
+    probe = dict(ein_el=np.array([1e-11, 1.0]), el_mat=np.zeros((2, len(s["energy_bins"]) - 1, 1)), ein_inel=None,
+                 inel_mat=None, nuinel_mat=None)
+    try:
+        lib.nuclide_file(options_of(s), th[0]["data"]["name"], th[0]["data"]["kT"], probe, s["energy_bins"],
+                         is_sab=True)
+    except lib.NdppError as e:
+        raise InputError(f"{th[0]['listing']['name']}: {e}") from None
+
+
+def write_library(run_dir, files: list, xml: bytes) -> list:
+    """Write every file under a temporary name, then rename them all; on any failure remove
+    what was written.  Returns the paths written."""
+    run_dir = Path(run_dir)
+    items = [(run_dir / name, data) for name, data in files if data is not None] + \
+            ([(run_dir / "ndpp_lib.xml", xml)] if xml else [])
+    tmp = []
+    try:
+        for path, data in items:
+            t = path.with_name(f".{path.name}.{os.getpid()}.tmp")
+            tmp.append(t)
+            t.write_bytes(data)
+        for (path, _), t in zip(items, tmp):
+            os.replace(t, path)
+    except BaseException:
+        for t in tmp:
+            t.unlink(missing_ok=True)
+        raise
+    return [p for p, _ in items]
+
+
+def run(run_dir, json_path=None, out=sys.stdout) -> int:
+    """The whole driver; returns the exit status."""
+    run_dir = Path(run_dir)
+    t_start = time.perf_counter()
+    try:
+        s = read_ndpp_xml(run_dir)
+        xs = read_cross_sections(s["cross_sections"])
+        tables = load_tables(s, xs)
+        if not tables:
+            raise InputError("no neutron or thermal tables to process")
+    except InputError as e:
+        print(f"ndpp_amd.run: input error: {e}", file=sys.stderr)
+        return EXIT_INPUT
+    try:
+        lib.load()
+        try:
+            _refuse_thermal_tabular(s, tables)
+        except InputError as e:
+            print(f"ndpp_amd.run: input error: {e}", file=sys.stderr)
+            return EXIT_INPUT
+        files, recs = compute(s, tables)
+        xml = lib_xml_of(s, run_dir, tables)
+    except (lib.NdppError, RuntimeError, OSError) as e:
+        print(f"ndpp_amd.run: library error: {e}", file=sys.stderr)
+        return EXIT_LIBRARY
+    try:
+        written = write_library(run_dir, files, xml)
+    except OSError as e:
+        print(f"ndpp_amd.run: cannot write the library: {e}", file=sys.stderr)
+        return EXIT_LIBRARY
+    total = time.perf_counter() - t_start
+    for r in recs:
+        print(f"{r['name']:>12s} {r['kind']:8s} {r['energies']['elastic']:7d} + {r['energies']['inelastic']:6d} E_in"
+              f"  -> {r['file']}", file=out)
+    print(f"{len(tables)} tables, {len(written)} files written in {total:.2f} s", file=out)
+    if json_path:
+        Path(json_path).write_text(json.dumps(dict(run_dir=str(run_dir), wall_s=total, scatt_type=s["scatt_type"],
+                                                   tables=recs), indent=1) + "\n")
+    return EXIT_OK
+
+
+def main(argv=None) -> int:
+    ap = argparse.ArgumentParser(prog="python -m ndpp_amd.run",
+                                 description="Build an NDPP library from <dir>/ndpp.xml and the ACE tables its "
+                                             "cross_sections.xml lists (exit 0: written, 2: input error, "
+                                             "3: library or device error; nothing is written on failure).")
+    ap.add_argument("run_dir", help="directory holding ndpp.xml; the library is written there")
+    ap.add_argument("--json", default=None, help="write per-table timings to this file")
+    a = ap.parse_args(argv)
+    return run(a.run_dir, a.json)
+
+
+if __name__ == "__main__":
+    sys.exit(main())
