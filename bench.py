@@ -25,6 +25,11 @@ N > 1  : weak scaling (default): whole nuclides per rank, which is the reference
          Launch: either a launcher that sets RANK / LOCAL_RANK / WORLD_SIZE (python -m
          torch.distributed.run ... bench.py --gpus N), or plain `python bench.py --gpus N`, which
          starts its own N rank processes (self_launch) and relays rank 0's line.
+--full : a plain run sets up, warms up, times the steps, writes --dump-outputs and prints the line
+         (with the figures derived from the timed steps themselves and the checks of their results).
+         Everything that costs work of its own is done only with --full: the CPU baseline and the
+         timed result's parity on its sample (every workload), N > 1's strong-scaling leg, the
+         one-GPU subsample check of --scaling strong, the library's per-nuclide bit check.
 """
 from __future__ import annotations
 
@@ -284,17 +289,19 @@ def library_main(a) -> None:
         ok = ok and bool((np.abs(r["el_mat"][fg][:, :, 0].sum(axis=1) - 1.0) < 1e-12).all())
         ok = ok and bool(np.isfinite(r["el_mat"]).all()) and (r["inel_mat"] is None or bool(np.isfinite(r["inel_mat"]).all()))
     ok = ok and all(bool(np.isfinite(m).all()) for m in sab) and all(bool(np.isfinite(c[0]).all()) for c in chi)
-    # five of this rank's nuclides again, one call each (ndpp_scatt_nuclide): the library pass -- every
-    # nuclide's free-gas elastic grid in ONE mixed batch -- must give the same bits (each
+    # --full: five of this rank's nuclides again, one call each (ndpp_scatt_nuclide): the library pass --
+    # every nuclide's free-gas elastic grid in ONE mixed batch -- must give the same bits (each
     # output element is produced by exactly one work item)
-    lib_check = {"nuclides": 0, "bit_identical_to_per_nuclide_calls": True}
-    for j in np.unique(np.linspace(0, len(mine) - 1, min(5, len(mine))).astype(int)) if mine else []:
-        one = ndpp_amd.scatt_nuclide(p, acen[j], bins, nuscatt=True)
-        same = all((res[j][k] is None and one[k] is None) or np.array_equal(res[j][k], one[k])
-                   for k in ("ein_el", "el_mat", "ein_inel", "inel_mat", "nuinel_mat"))
-        lib_check["nuclides"] += 1
-        lib_check["bit_identical_to_per_nuclide_calls"] = lib_check["bit_identical_to_per_nuclide_calls"] and bool(same)
-    ok = ok and lib_check["bit_identical_to_per_nuclide_calls"]
+    lib_check = None
+    if a.full:
+        lib_check = {"nuclides": 0, "bit_identical_to_per_nuclide_calls": True}
+        for j in np.unique(np.linspace(0, len(mine) - 1, min(5, len(mine))).astype(int)) if mine else []:
+            one = ndpp_amd.scatt_nuclide(p, acen[j], bins, nuscatt=True)
+            same = all((res[j][k] is None and one[k] is None) or np.array_equal(res[j][k], one[k])
+                       for k in ("ein_el", "el_mat", "ein_inel", "inel_mat", "nuinel_mat"))
+            lib_check["nuclides"] += 1
+            lib_check["bit_identical_to_per_nuclide_calls"] = lib_check["bit_identical_to_per_nuclide_calls"] and bool(same)
+        ok = ok and lib_check["bit_identical_to_per_nuclide_calls"]
     ok = R.reduce(1.0 if ok else 0.0, "min") == 1.0
     counts = np.array([n_fg, n_el, n_inel, sum(len(g) for g in sab_grids), sum(len(g) for g in chi_grids)], dtype=np.float64)
     parts = R.gather(counts)
@@ -338,10 +345,15 @@ def main() -> None:
     ap.add_argument("--warmup", type=int, default=0)
     ap.add_argument("--nein", type=int, default=100000)
     ap.add_argument("--order", type=int, default=6, help="L = scatt_order + 1 (P5 -> 6)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need (CPU baseline and the "
+                         "parity of the timed result on its sample, N > 1's strong-scaling leg, the one-GPU "
+                         "check of --scaling strong, the library's per-nuclide check); off: only the timed "
+                         "steps, the dump and the result line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--cpu-sample", type=int, default=1024,
-                    help="points of the stratified subsample the CPU baseline is timed on (SURVEY 8d / BASELINE.md "
-                         "section 3: 1024; about 75 s on the 16 cores of a GPU box)")
+                    help="--full: points of the stratified subsample the CPU baseline is timed on (SURVEY 8d / "
+                         "BASELINE.md section 3: 1024; about 75 s on the 16 cores of a GPU box)")
     ap.add_argument("--workload", default="freegas",
                     help="freegas (BASELINE.json's headline, default) or one of the secondary "
                          "kernels in bench_kernels.NAMES (single GPU)")
@@ -350,10 +362,10 @@ def main() -> None:
                          "the multi-rank path on a one-GPU box with --share-device)")
     ap.add_argument("--scaling", default="weak", choices=["strong", "weak"],
                     help="N>1: weak = one nuclide (a full grid) per rank, the reference's own partition "
-                         "(default; the line then also carries a strong-scaling leg timed after it); "
+                         "(default; with --full the line also carries a strong-scaling leg timed after it); "
                          "strong = the one grid dealt over the ranks is the timed workload")
     ap.add_argument("--strong-leg-steps", type=int, default=2,
-                    help="N>1, weak scaling: passes of the strong-scaling leg reported beside the "
+                    help="N>1, weak scaling, --full: passes of the strong-scaling leg reported beside the "
                          "timed value (0: none)")
     ap.add_argument("--barrier", default="file", choices=["file", "rccl"],
                     help="how the ranks of N>1 meet for the timing barrier and the MAX of the elapsed "
@@ -442,9 +454,10 @@ def main() -> None:
     p0 = res[:, :, 0].sum(axis=1)
     ok = bool((np.abs(p0 - 1.0) < 1e-12).all()) and int(np.abs(res_status).sum()) == 0
     shard_check = None
-    if strong:
-        # the gathered grid against a ONE-GPU call on a stratified subsample, bit for bit (each
-        # output element is produced by exactly one work item: SURVEY 8e's determinism contract)
+    if strong and (a.full or a.dump_outputs):
+        # rank 0 gathers the one grid's rows (to dump them) and, under --full, checks them against a
+        # ONE-GPU call on a stratified subsample, bit for bit (each output element is produced by
+        # exactly one work item: SURVEY 8e's determinism contract)
         parts = R.gather(res.reshape(-1))
         status_parts = R.gather(res_status.astype(np.float64)) if a.dump_outputs else None
         if rank == 0:
@@ -455,12 +468,13 @@ def main() -> None:
                 res_status = np.zeros(a.nein)
                 for r, part in enumerate(status_parts):
                     res_status[nd.interleaved_shard(a.nein, world, r)] = np.asarray(part)
-            sub = np.unique(np.linspace(0, a.nein - 1, min(a.nein, 96)).astype(np.int64))
-            one, _ = ndpp_amd.elastic_leg_batch(p, wl["A"], wl["kT"], 1e300, 0.0, wl["ein"][sub],
-                                                wl["row_lo"][sub], wl["w_hi"][sub], wl["f_tab"], wl["bins"])
-            same = bool(np.array_equal(one, full[sub]))
-            shard_check = {"points": int(len(sub)), "bit_identical_to_one_gpu_call": same}
-            ok = ok and same
+            if a.full:
+                sub = np.unique(np.linspace(0, a.nein - 1, min(a.nein, 96)).astype(np.int64))
+                one, _ = ndpp_amd.elastic_leg_batch(p, wl["A"], wl["kT"], 1e300, 0.0, wl["ein"][sub],
+                                                    wl["row_lo"][sub], wl["w_hi"][sub], wl["f_tab"], wl["bins"])
+                same = bool(np.array_equal(one, full[sub]))
+                shard_check = {"points": int(len(sub)), "bit_identical_to_one_gpu_call": same}
+                ok = ok and same
             res = full
     weak_check = strong_leg = None
     if world > 1 and not strong:
@@ -470,7 +484,7 @@ def main() -> None:
             same = all(bytes(np.asarray(d, dtype=np.uint8)) == bytes(np.asarray(digs[0], dtype=np.uint8)) for d in digs)
             weak_check = {"ranks": world, "results_bit_identical_across_ranks": bool(same)}
             ok = ok and same
-        if a.strong_leg_steps > 0 and a.nein >= world:      # (every rank needs a point of the grid)
+        if a.full and a.strong_leg_steps > 0 and a.nein >= world:      # (every rank needs a point of the grid)
             # strong-scaling leg (reported beside `value`, never part of it): the one grid dealt
             # round-robin, this rank's shard timed between barriers, MAX over ranks -- and the
             # shard's rows must be the bits of the same energies in the full-grid result above
@@ -633,7 +647,7 @@ def main() -> None:
             # the moments and status words of the last timed step: all incoming energies (the shard's
             # under --emulate-rank), in the order of the workload's grid
             line["outputs_dumped"] = dump_outputs(a.dump_outputs, {"moments": res, "status": res_status})
-        if world == 1 and not a.no_cpu_baseline:
+        if world == 1 and a.full and not a.no_cpu_baseline:
             try:
                 import tempfile
                 dump = Path(tempfile.gettempdir()) / f"ndpp_cpu_sample_{os.getpid()}.npz"

@@ -2,7 +2,7 @@
 kernels of SURVEY.md 8(a) -- file4-CM, file6 CM/lab, law 9, S(alpha,beta), chi --
 on synthetic tables of the SURVEY 8(d) config-3/4/5 shapes, each with the same JSON
 line as the headline (value = device time of the kernels, inputs resident; the
-PCIe-inclusive wall rate is reported beside it) and the CPU port timed on a sample.
+PCIe-inclusive wall rate is reported beside it) and, with --full, the CPU port timed on a sample.
 
 make(name) is shared with oracle/cpu_baseline.py so both legs see the same inputs.
 """
@@ -311,7 +311,7 @@ def main(a) -> None:
     if a.dump_outputs:
         from bench import dump_outputs
         line["outputs_dumped"] = dump_outputs(a.dump_outputs, {"out": out})
-    if not a.no_cpu_baseline:
+    if a.full and not a.no_cpu_baseline:
         try:
             r = subprocess.run([sys.executable, str(ROOT / "oracle" / "cpu_baseline.py"),
                                 "--workload", a.workload], capture_output=True, text=True, timeout=900)

@@ -87,14 +87,15 @@ def test_gpu_library_equals_per_nuclide_calls_and_reference(hip):
 @pytest.mark.gpu
 def test_gpu_library_bench_two_ranks_on_one_device():
     """bench.py --workload library --gpus 2 (two worker processes sharing cuda:0): every table kind,
-    whole tables dealt by the cost model, results_ok reduced over the ranks."""
+    whole tables dealt by the cost model, results_ok (with --full: the per-nuclide bit check too)
+    reduced over the ranks."""
     procs = []
     for rank in range(2):
         env = dict(os.environ, RANK=str(rank), LOCAL_RANK=str(rank), WORLD_SIZE="2",
                    MASTER_ADDR="127.0.0.1", MASTER_PORT="29761")
         cmd = [sys.executable, str(ROOT / "bench.py"), "--workload", "library", "--gpus", "2", "--steps", "1",
                "--warmup", "0", "--library-size", "10", "--library-thermal", "2", "--library-fissionable", "2",
-               "--share-device"]
+               "--share-device", "--full"]
         procs.append(subprocess.Popen(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
     outs = [q.communicate(timeout=290) for q in procs]
     assert all(q.returncode == 0 for q in procs), "\n".join(o[0] + o[1] for o in outs)
@@ -102,3 +103,4 @@ def test_gpu_library_bench_two_ranks_on_one_device():
     assert line["n_gpus"] == 2 and line["scaling"] == "strong" and line["results_ok"] is True
     ie = line["config"]["incoming_energies"]
     assert ie["free_gas_elastic"] > 0 and ie["inelastic"] > 0 and ie["thermal"] > 0 and ie["chi"] > 0
+    assert line["library_check_rank0"]["bit_identical_to_per_nuclide_calls"] is True

@@ -7,9 +7,9 @@ an integration failure here must never hide kernel parity under `pytest -x` agai
     guard on sys.meta_path and `import torch` raises ImportError at once (round 2 tried to make
     that order work by preloading the wheel's runtime; the driver's run of it hung, see
     tools/diag_load_order.py and DESIGN.md section 7).
-(2) bench.py's N = 2 path: the headline grid dealt over two ranks that share the one GPU of the
-    box, met through ndpp_amd.dist.FileRendezvous or torch.distributed, gathered and checked
-    against a one-GPU call bit for bit.
+(2) bench.py's N = 2 path (with --full, which adds the checks below): the headline grid dealt over
+    two ranks that share the one GPU of the box, met through ndpp_amd.dist.FileRendezvous or
+    torch.distributed, gathered and checked against a one-GPU call bit for bit.
 Every worker runs `python -u`, writes a flushed marker per stage to stderr and arms faulthandler,
 so a stall names its stage; every child process group is killed when its time is up."""
 import json
@@ -20,6 +20,7 @@ import sys
 import uuid
 from pathlib import Path
 
+import numpy as np
 import pytest
 
 ROOT = Path(__file__).resolve().parent.parent
@@ -140,7 +141,7 @@ def _two_ranks(barrier, port, extra, tmp_path):
         env = dict(os.environ, RANK=str(rank), LOCAL_RANK=str(rank), WORLD_SIZE="2",
                    MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), NDPP_RDZV_TAG=tag)
         cmd = [sys.executable, "-u", str(ROOT / "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0",
-               "--no-cpu-baseline", "--share-device", "--barrier", barrier, "--backend", "gloo", *extra]
+               "--full", "--no-cpu-baseline", "--share-device", "--barrier", barrier, "--backend", "gloo", *extra]
         procs.append(subprocess.Popen(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
                                       text=True, start_new_session=True))
     outs = []
@@ -203,7 +204,7 @@ def test_two_ranks_under_the_real_launcher(tmp_path):
     the launcher's environment (file rendezvous keyed on the launcher's pid)."""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", "29743", str(ROOT / "bench.py"),
-           "--gpus", "2", "--steps", "1", "--warmup", "0", "--nein", "128", "--no-cpu-baseline",
+           "--gpus", "2", "--steps", "1", "--warmup", "0", "--nein", "128", "--full", "--no-cpu-baseline",
            "--share-device"]
     rc, out, err = run_group(cmd, 240, cwd=str(tmp_path))
     assert rc == 0, f"rc {rc}\n{out}\n{err}"
@@ -223,7 +224,8 @@ def test_bench_starts_its_own_ranks_from_a_bare_shell(workload, tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "NDPP_RDZV_TAG")}
     extra = ["--nein", "4096"] if workload == "freegas" else \
         ["--workload", "library", "--library-size", "6", "--library-thermal", "2", "--library-fissionable", "2"]
-    cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--share-device", "--no-cpu-baseline", *extra]
+    cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--share-device", "--full", "--no-cpu-baseline",
+           *extra]
     rc, out, err = run_group(cmd, 400, env=env, cwd=str(tmp_path))
     assert rc == 0, f"rc {rc}\n{out}\n{err}"
     lines = [l for l in out.splitlines() if l.startswith("{")]
@@ -246,3 +248,25 @@ def test_bench_launcher_fails_when_a_rank_fails(tmp_path):
     rc, out, err = run_group(cmd, 200, env=env, cwd=str(tmp_path))
     assert rc not in (0, None), f"rc {rc}\n{out}\n{err}"
     assert "bench.py launcher: rank" in err and "\"metric\"" not in out
+
+
+@pytest.mark.gpu
+def test_plain_bench_run_leaves_the_rest_to_full(tmp_path):
+    """`python bench.py` without --full: the timed steps, the dump and the line, no CPU baseline and
+    no parity on its sample.  With --full (a small CPU sample) both are back, the parity within its
+    tolerance, and the timed step dumps the same bits as the plain run's."""
+    base = [sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "0", "--nein", "512"]
+    rc, out, err = run_group(base + ["--dump-outputs", str(tmp_path / "plain")], 240, cwd=str(tmp_path))
+    assert rc == 0, f"rc {rc}\n{out}\n{err}"
+    plain = json.loads(out.strip().splitlines()[-1])
+    assert plain["results_ok"] is True and plain["ms_per_step"] > 0 and plain["steps"] == 1
+    assert not {"cpu_baseline", "cpu_baseline_port", "parity_on_cpu_sample"} & set(plain)
+    rc, out, err = run_group(base + ["--full", "--cpu-sample", "16", "--dump-outputs", str(tmp_path / "full")],
+                             400, cwd=str(tmp_path))
+    assert rc == 0, f"rc {rc}\n{out}\n{err}"
+    full = json.loads(out.strip().splitlines()[-1])
+    assert full["results_ok"] is True and full["cpu_baseline"]["value"] > 0, full.get("cpu_baseline")
+    par = full["parity_on_cpu_sample"]
+    assert par["n"] == 16 and par["max_scale_rel_err"] < par["tolerance"]
+    for name in ("moments", "status"):
+        assert np.array_equal(np.load(tmp_path / "plain" / f"{name}.npy"), np.load(tmp_path / "full" / f"{name}.npy"))

@@ -8,7 +8,7 @@ O=gpurun_out/r04; mkdir -p $O
 parts="${*:-stats sq traffic headline n2 secondary u238 library clock}"   # (headline after the counter passes: its line quotes them)
 for p in $parts; do case $p in
 headline)
-  timeout -k 10 500 python3 bench.py --steps 2 --warmup 1 > $O/bench_nein100000_P5.json 2> $O/bench_nein100000_P5.err || exit 1
+  timeout -k 10 500 python3 bench.py --full --steps 2 --warmup 1 > $O/bench_nein100000_P5.json 2> $O/bench_nein100000_P5.err || exit 1
   cut -c1-300 $O/bench_nein100000_P5.json ;;
 stats)
   rm -rf $O/prof_headline
@@ -35,13 +35,13 @@ traffic)
   python3 tools/pmc_traffic_summary.py r04 1 > $O/pmc_traffic.txt; cp gpurun_out/pmc_r04_traffic.json $O/pmc_traffic_bench_nein100000_P5.json; cp gpurun_out/pmc_r04_traffic.json profiles/r04/pmc_traffic_bench_nein100000_P5.json; head -4 $O/pmc_traffic.txt ;;
 n2)
   for r in 0 1; do
-    NDPP_RDZV_TAG=profile_n2_$$ RANK=$r LOCAL_RANK=$r WORLD_SIZE=2 MASTER_ADDR=127.0.0.1 MASTER_PORT=29751 timeout -k 10 400 python3 bench.py --gpus 2 --steps 1 --warmup 0 --no-cpu-baseline --share-device > $O/bench_2ranks_shared_gpu_rank$r.json 2> $O/bench_2ranks_rank$r.err &
+    NDPP_RDZV_TAG=profile_n2_$$ RANK=$r LOCAL_RANK=$r WORLD_SIZE=2 MASTER_ADDR=127.0.0.1 MASTER_PORT=29751 timeout -k 10 400 python3 bench.py --gpus 2 --steps 1 --warmup 0 --full --no-cpu-baseline --share-device > $O/bench_2ranks_shared_gpu_rank$r.json 2> $O/bench_2ranks_rank$r.err &
   done
   wait; cut -c1-400 $O/bench_2ranks_shared_gpu_rank0.json ;;
 secondary)
   mkdir -p $O/kernels
   for w in file4 file6cm file6cm_g70 file6lab file6lab_g70 law9 sab_disc sab_cont chi; do
-    timeout -k 10 300 python3 bench.py --workload $w --steps 3 --warmup 1 > $O/kernels/$w.json 2> $O/kernels/$w.err; cut -c1-200 $O/kernels/$w.json
+    timeout -k 10 300 python3 bench.py --workload $w --full --steps 3 --warmup 1 > $O/kernels/$w.json 2> $O/kernels/$w.err; cut -c1-200 $O/kernels/$w.json
   done
   cat $O/kernels/*.json > $O/bench_secondary_kernels.jsonl
   for w in file4 file6cm_g70 file6lab_g70; do
@@ -54,7 +54,7 @@ u238)
     timeout -k 10 500 python3 bench.py --workload $w --steps 1 --warmup 0 > $O/bench_${w}_whole_nuclide.json 2> $O/bench_$w.err; cut -c1-200 $O/bench_${w}_whole_nuclide.json
   done ;;
 library)
-  timeout -k 10 500 python3 bench.py --workload library > $O/bench_library_423.json 2> $O/bench_library.err; cut -c1-200 $O/bench_library_423.json ;;
+  timeout -k 10 500 python3 bench.py --workload library --full > $O/bench_library_423.json 2> $O/bench_library.err; cut -c1-200 $O/bench_library_423.json ;;
 scaling)
   # PROJECTION of the 1/2/4/8-GPU strong-scaling curve on one GPU: rank 0's shard of the one grid
   for n in 1 2 4 8; do
