@@ -375,22 +375,139 @@ template <int R, int LMAX>
 void launch_gauss(const FgBatch& B, int level, hipStream_t s) {
   hipLaunchKernelGGL((fg_gauss_kernel<R, LMAX>), dim3(4096), dim3(256), 0, s, B, level);
 }
+
+// The same work as phases (fg_pipeline.h mu_gauss_phase), each run by a whole wave: a wave pulls
+// 64-task chunks of the level from a counter and keeps one LDS queue per (kind, phase) -- kind: far or
+// near, which differ in depth and rules.  A phase runs when 64 candidates have reached it; those
+// that go on are pushed to the queue of their next phase, those that fail or finish free their
+// lane.  Nothing depends on which candidates share a wave: the decisions, the rows and the values
+// are mu_gauss_task's.  Queue invariant: between runs, at most one queue PER KIND holds 64 or more
+// (after the entry pushes: the far and the near entry queue may both), and none holds 128: a queue
+// is fed only by the one phase before it of its own kind (or the entry, at most 64 at a time), and
+// pump runs the earliest full queue first.
+constexpr int kGaussQueues = 2 * kGaussPhases;      // index kind * kGaussPhases + phase
+// Waves per SIMD asked of the compiler: three where up to 12 channels fit in 168 VGPRs (at <2, 6>, the
+// headline's shape, with ~100 bytes of spill: 281 -> 270 ms per pass measured against two waves);
+// two for the wider shapes, which would spill hundreds of bytes at three.
+template <int R, int LMAX>
+constexpr int kGaussWavesPerEU = (R * LMAX <= 12 && LMAX <= 8) ? 3 : 2;
+template <int R, int LMAX>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kGaussWavesPerEU<R, LMAX>, kGaussWavesPerEU<R, LMAX>)))
+void fg_gauss_phased_kernel(FgBatch B, int level, int* counter) {
+  constexpr int kWaves = 256 / kWave;
+  __shared__ int q_t[kWaves][kGaussQueues][2 * kWave];
+  __shared__ unsigned char q_st[kWaves][kGaussQueues][2 * kWave];
+  __shared__ int q_n[kWaves][kGaussQueues];
+  if (*B.overflow) return;
+  const int base = B.lvl_off(level);
+  const int nt = B.n_tasks(level);
+  const int lane = threadIdx.x & (kWave - 1);
+  const int w = threadIdx.x / kWave;
+  const unsigned long long below = (1ull << lane) - 1ull;
+  int* qn = q_n[w];
+  for (int k = lane; k < kGaussQueues; k += kWave) qn[k] = 0;
+  __builtin_amdgcn_wave_barrier();
+  unsigned long long nk = 0, ni = 0;
+  // the candidates of lanes with `go` set, all bound for queue k
+  auto push = [&](bool go, int k, int t, unsigned st) {
+    const unsigned long long m = __builtin_amdgcn_ballot_w64(go);
+    const int at = qn[k];
+    if (go) {
+      const int i = at + __popcll(m & below);
+      q_t[w][k][i] = t;
+      q_st[w][k][i] = (unsigned char)st;
+    }
+    __builtin_amdgcn_wave_barrier();
+    qn[k] = at + __popcll(m);
+    __builtin_amdgcn_wave_barrier();
+  };
+  // the phase of queue k on the (at most 64) candidates on top of it
+  auto run = [&](int k) {
+    const int kind = k >= kGaussPhases, p = k - kind * kGaussPhases;
+    const int have = qn[k], n = have < kWave ? have : kWave;
+    const bool act = lane < n;
+    GaussCand c{0, 0u};
+    if (act) {
+      c.t = q_t[w][k][have - n + lane];
+      c.st = q_st[w][k][have - n + lane];
+    }
+    __builtin_amdgcn_wave_barrier();
+    qn[k] = have - n;
+    __builtin_amdgcn_wave_barrier();
+    int next = kGaussPhases;
+    if (act) {
+      const int ke = mu_gauss_phase<R, LMAX>(B, level, base, p, c, next);
+      nk += (unsigned long long)ke;
+      // (every row of the job by the rule)
+      ni += (next == kGaussPhases && B.t_gl[c.t] == (1u << R) - 1u) ? 1ull : 0ull;
+    }
+    // one kind per queue: the phase after p is the same for every candidate that goes on
+    const int np = gauss_next_phase(B, p, kind ? kGaussNear : 0u);
+    push(act && next < kGaussPhases, kind * kGaussPhases + (np < kGaussPhases ? np : 0), c.t, c.st);
+  };
+  // a full queue first (the earliest); with `flush`, then the remainder of the earliest phase
+  auto pump = [&](bool flush) {
+    for (;;) {
+      int k = -1;
+      for (int j = 0; j < kGaussQueues; ++j)
+        if (k < 0 && qn[j] >= kWave) k = j;
+      for (int j = 0; flush && j < kGaussQueues; ++j)
+        if (k < 0 && qn[j] > 0) k = j;
+      if (k < 0) return;
+      run(k);
+    }
+  };
+  const int p_far = gauss_next_phase(B, -1, 0u), p_near = kGaussPhases + gauss_next_phase(B, -1, kGaussNear);
+  for (bool more = true; more;) {
+    int t0 = 0;
+    if (lane == 0) t0 = atomicAdd(counter, kWave);
+    t0 = __shfl(t0, 0);
+    more = t0 < nt;
+    const int t = t0 + lane;
+    unsigned st = 0;
+    if (t < nt && B.t_gl[t]) st = mu_gauss_entry<R>(B, level, base, t);
+    push(st != 0 && !(st & kGaussNear), p_far, t, st);
+    push(st & kGaussNear, p_near, t, st);
+    pump(!more);                                     // (one call site: the phases inline once)
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    nk += __shfl_down(nk, o);
+    ni += __shfl_down(ni, o);
+  }
+  if (lane == 0 && (nk | ni)) {
+    atomicAdd(&B.stats[kStatKEvals], nk);
+    atomicAdd(&B.stats[kStatGaussIntegrals], ni);
+  }
+}
+// persistent: a few blocks per CU, the chunks handed out by the counter (zeroed with the chunk's)
+constexpr int kGaussBlocksPerCU = 8;
+template <int R, int LMAX>
+void launch_gauss_phased(const FgBatch& B, int level, int num_cu, hipStream_t s) {
+  int* counter = B.next_task + (kMaxLevels + 2) + level;
+  hipLaunchKernelGGL((fg_gauss_phased_kernel<R, LMAX>), dim3(num_cu * kGaussBlocksPerCU), dim3(256), 0, s, B,
+                     level, counter);
+}
 #endif
-void launch_gauss_any(const FgBatch& B, int level, hipStream_t s) {
+// the Gauss stage of a level: phased (default) or one candidate per lane (phased = false: the
+// kernel of the previous version, kept for comparison, NDPP_HIP_GAUSS_PHASED=0)
+void launch_gauss_any(const FgBatch& B, int level, int num_cu, bool phased, hipStream_t s) {
 #if NDPP_FAST
   if (!B.t_gl) return;
+#define NDPP_GAUSS_LAUNCH(R_, L_) \
+  (phased ? launch_gauss_phased<R_, L_>(B, level, num_cu, s) : launch_gauss<R_, L_>(B, level, s))
   if (B.R == 2) {
-    if (B.L <= 4) launch_gauss<2, 4>(B, level, s);
-    else if (B.L <= 6) launch_gauss<2, 6>(B, level, s);
-    else launch_gauss<2, 8>(B, level, s);
+    if (B.L <= 4) NDPP_GAUSS_LAUNCH(2, 4);
+    else if (B.L <= 6) NDPP_GAUSS_LAUNCH(2, 6);
+    else NDPP_GAUSS_LAUNCH(2, 8);
     return;
   }
-  if (B.L <= 4) launch_gauss<1, 4>(B, level, s);
-  else if (B.L <= 6) launch_gauss<1, 6>(B, level, s);
-  else if (B.L <= 8) launch_gauss<1, 8>(B, level, s);
-  else launch_gauss<1, 11>(B, level, s);
+  if (B.L <= 4) NDPP_GAUSS_LAUNCH(1, 4);
+  else if (B.L <= 6) NDPP_GAUSS_LAUNCH(1, 6);
+  else if (B.L <= 8) NDPP_GAUSS_LAUNCH(1, 8);
+  else NDPP_GAUSS_LAUNCH(1, 11);
+#undef NDPP_GAUSS_LAUNCH
 #else
-  (void)B; (void)level; (void)s;
+  (void)B; (void)level; (void)num_cu; (void)phased; (void)s;
 #endif
 }
 

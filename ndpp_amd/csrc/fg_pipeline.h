@@ -134,7 +134,7 @@ struct FgBatch {
   int gl_graded = 8;           // near candidates: levels of the graded rule tried first (0: off)
   // ---- counters
   int* lvl_cnt;   // [kMaxLevels+1] nodes per outer level
-  int* next_task; // [kMaxLevels+1] dynamic task counters of the mu kernel
+  int* next_task; // [2][kMaxLevels+2] dynamic task counters per level: the mu kernel's, the Gauss stage's
   int* overflow;  // [1] set when ncap was too small
   unsigned long long* stats;  // [kNumStats]
   // ---- split mode: a level with at most split_below inner integrals is walked by
@@ -511,15 +511,17 @@ constexpr double kGaussAgree = 1.0E-13;
 constexpr int kCertDepth = 5;
 constexpr double kCertBig = 64.0;
 
+// Certification of levels [dep_lo, dep_hi) -> the rows of `rows` that pass (see above); `evals` counts
+// the kernel values evaluated.  Level by level, left to right; a node takes its left end from its left
+// neighbour and evaluates its other four points (no per-lane arrays: four kernel values per node
+// instead of the tree's two, all in registers; at level 0 the prep stage's midpoint and right end).
+// The dyadic points are a + i (b - a) / 2^k here, the walk's nested midpoints there: an ulp apart at
+// most, which cannot turn an acceptance into a refinement that matters -- the nodes this looks for
+// accept by a wide margin.  The neighbour rule pairs nodes of one level only, so a range of whole
+// levels is certified the same way whatever ran before it.
 template <int R, int LMAX>
 NDPP_HD unsigned mu_gauss_certify(const FgBatch& B, const FgPair& q, const FView<R>& fv, int t, unsigned mask,
-                                  unsigned rows, int cert_depth, const PnConsts& pk) {
-  // -> the rows of `rows` that pass (see above).
-  // Level by level, left to right; a node takes its left end from its left neighbour and evaluates
-  // its other four points (no per-lane arrays: four kernel values per node instead of the tree's
-  // two, all in registers).  The dyadic points are a + i (b - a) / 2^k here, the walk's nested midpoints there:
-  // an ulp apart at most, which cannot turn an acceptance into a refinement that matters -- the
-  // nodes this looks for accept by a wide margin.
+                                  unsigned rows, int dep_lo, int dep_hi, const PnConsts& pk, int& evals) {
   const double a = B.t_mulo[t], b = B.t_muhi[t];
   auto Kat = [&](double mu0, double mu1, double* K0, double* K1) {
     FvLoad v0[R], v1[R];
@@ -533,7 +535,7 @@ NDPP_HD unsigned mu_gauss_certify(const FgBatch& B, const FgPair& q, const FView
       K1[r] = (q.C1 * fg_fval_use(v1[r])) * E1;
     }
   };
-  for (int dep = 0; dep < cert_depth; ++dep) {
+  for (int dep = dep_lo; dep < dep_hi; ++dep) {
     // the reference's depth limit: it accepts every node of this level, converged or not, and a
     // converged Gauss value is not what it computes -- the row goes to the walk (fg_gauss_box keeps
     // such tunables away from this stage; this is the safeguard)
@@ -558,13 +560,17 @@ NDPP_HD unsigned mu_gauss_certify(const FgBatch& B, const FgPair& q, const FView
       const double xc = 0.5 * (xa + xb), xd = 0.5 * (xa + xc), xe = 0.5 * (xc + xb);
       double Kd[R], Ke[R], Kc[R], Kb[R];
       Kat(xd, xe, Kd, Ke);
-      Kat(xc, xb, Kc, Kb);
       if (dep == 0) {
 #pragma unroll
         for (int r = 0; r < R; ++r) { Kc[r] = B.tX(2, r, t); Kb[r] = B.tX(1, r, t); }
-      } else if (j == nn - 1) {
+        evals += 2;
+      } else {
+        Kat(xc, xb, Kc, Kb);
+        if (j == nn - 1) {
 #pragma unroll
-        for (int r = 0; r < R; ++r) Kb[r] = B.tX(1, r, t);
+          for (int r = 0; r < R; ++r) Kb[r] = B.tX(1, r, t);
+        }
+        evals += 4;
       }
       double Pd[LMAX], Pc[LMAX], Pe[LMAX], Pb[LMAX];
       pn_all<LMAX>(xd, Pd, pk); pn_all<LMAX>(xc, Pc, pk); pn_all<LMAX>(xe, Pe, pk); pn_all<LMAX>(xb, Pb, pk);
@@ -600,21 +606,76 @@ NDPP_HD unsigned mu_gauss_certify(const FgBatch& B, const FgPair& q, const FView
   return rows;
 }
 
-template <int R, int LMAX>
-NDPP_HD int mu_gauss_task(const FgBatch& B, int level, int base, int t) {
+// The stage runs as PHASES: certification of the strict levels 0 ... kCertDepth - 1, of the
+// neighbour-rule levels kCertDepth ... depth - 1, the graded rule (near candidates), the panel
+// ladder.  A candidate that fails leaves after its phase, so the device (fg_gauss_phased_kernel)
+// hands each phase to a wave of candidates that have all reached it; mu_gauss_task runs the phases
+// of one candidate in turn.  Same functions, same decisions, same values.  (Measured on the
+// headline, profiles/gauss_phases/: the strict levels reject 15 % of the far and 9 % of the near
+// candidates, the graded rule leaves 37 % of the near ones to the ladder, the neighbour levels
+// reject 0.03 % -- one phase per neighbour level bought no compaction, only queue traffic.)
+constexpr int kGaussCertPhases = 2;
+constexpr int kGaussPhGraded = kGaussCertPhases;
+constexpr int kGaussPhLadder = kGaussCertPhases + 1;
+constexpr int kGaussPhases = kGaussCertPhases + 2;
+NDPP_HD int gauss_cert_split(int p) {        // first level of certification phase p (p = 2: no end)
+  return p == 0 ? 0 : p == 1 ? kCertDepth : kMaxLevels;
+}
+
+// What a candidate carries from one phase to the next: its task record and its rows -- those still
+// in play (bits 0 .. R-1), those a rule has already taken (bits kGaussDone ..), kGaussNear.
+constexpr int kGaussDone = 2;
+static_assert(kMaxRows <= kGaussDone, "rows in play and rows done share one byte with kGaussNear");
+struct GaussCand {
+  int t;
+  unsigned st;
+};
+
+NDPP_HD int gauss_cert_depth(const FgBatch& B, unsigned st) {
+  return (st & kGaussNear) ? B.gl_cert_depth_near : B.gl_cert_depth;
+}
+// does phase p have anything to do for a candidate of this kind (far / near)?
+NDPP_HD bool gauss_phase_on(const FgBatch& B, int p, unsigned st) {
+  if (p < kGaussCertPhases) return gauss_cert_split(p) < gauss_cert_depth(B, st);
+  if (p == kGaussPhGraded) return (st & kGaussNear) && B.gl_graded > 0;
+  return p == kGaussPhLadder;
+}
+// the first phase after p that has (kGaussPhases: none)
+NDPP_HD int gauss_next_phase(const FgBatch& B, int p, unsigned st) {
+  do ++p; while (p < kGaussPhases && !gauss_phase_on(B, p, st));
+  return p;
+}
+
+// Entry to the stage: a flagged task record -> the candidate's state (0: nothing to do; t_gl is
+// cleared when the flag was set but no row has a channel left).
+template <int R>
+NDPP_HD unsigned mu_gauss_entry(const FgBatch& B, int level, int base, int t) {
   unsigned rows = B.t_gl[t];
   if (!rows) return 0;
-  const bool near = (rows & kGaussNear) != 0;
-  const int cert_depth = near ? B.gl_cert_depth_near : B.gl_cert_depth;
+  const unsigned near = rows & kGaussNear;
   rows &= ~kGaussNear;
-  int n_node, slot;
-  if (level == 0) { n_node = t / 5; slot = t - 5 * n_node; }
-  else { n_node = base + (t >> 1); slot = 1 + 2 * (t & 1); }
+  const int n_node = level == 0 ? t / 5 : base + (t >> 1);
   const unsigned mask = (unsigned)B.node_info[4 * n_node + 0];
 #pragma unroll
   for (int r = 0; r < R; ++r)
     if (!(mask & (((1u << kRowBits) - 1u) << (r * kRowBits)))) rows &= ~(1u << r);   // nothing to do for the row
   if (rows == 0) { B.t_gl[t] = 0; return 0; }
+  return rows | near;
+}
+
+// Phase p of one candidate.  -> kernel values evaluated; c.st is updated, and `next` is the phase the
+// candidate goes on to, or kGaussPhases when it is finished (its t_gl entry then holds the rows the
+// rules took, 0 when the walk takes them all).
+template <int R, int LMAX>
+NDPP_HD int mu_gauss_phase(const FgBatch& B, int level, int base, int p, GaussCand& c, int& next) {
+  const int t = c.t;
+  const unsigned near = c.st & kGaussNear;
+  unsigned rows = c.st & ((1u << R) - 1u);
+  unsigned done = (c.st >> kGaussDone) & ((1u << R) - 1u);
+  int n_node, slot;
+  if (level == 0) { n_node = t / 5; slot = t - 5 * n_node; }
+  else { n_node = base + (t >> 1); slot = 1 + 2 * (t & 1); }
+  const unsigned mask = (unsigned)B.node_info[4 * n_node + 0];
   const int job = B.node_job(n_node);
   const double Ein = B.job_ein[job];
   const double Eout = fg_slot_point(B.node_a[n_node], B.node_b[n_node], slot);
@@ -624,17 +685,24 @@ NDPP_HD int mu_gauss_task(const FgBatch& B, int level, int base, int t) {
   const FView<R> fv = f_view<R>(B.f_tab, f, B.M);
   const double a = B.t_mulo[t], b = B.t_muhi[t];
   const PnConsts pk = make_pn_consts();
-  rows = mu_gauss_certify<R, LMAX>(B, q, fv, t, mask, rows, cert_depth, pk);
-  if (rows == 0) {
-    B.t_gl[t] = 0;
-    return 4 * ((1 << cert_depth) - 1);
+  int evals = 0;
+  auto finish = [&](unsigned taken) {
+    B.t_gl[t] = (unsigned char)taken;
+    next = kGaussPhases;
+  };
+  if (p < kGaussCertPhases) {
+    const int cd = gauss_cert_depth(B, c.st);
+    const int hi = gauss_cert_split(p + 1) < cd ? gauss_cert_split(p + 1) : cd;
+    rows = mu_gauss_certify<R, LMAX>(B, q, fv, t, mask, rows, gauss_cert_split(p), hi, pk, evals);
+    if (rows == 0) { finish(0u); return evals; }
+    c.st = near | rows;
+    next = gauss_next_phase(B, p, c.st);
+    return evals;
   }
   // the rule with n panels against the one with n / 2, n doubled until every row left agrees (or
   // B.gl_panels is reached: the rows that still disagree are walked).  A row takes the value of the
   // first rule that agrees for IT, whatever the job's other row needs (joint == single-row bits).
   double Ic[R * LMAX], If[R * LMAX];
-  int evals = 4 * ((1 << cert_depth) - 1);
-  unsigned done = 0;
   auto take_agreeing_rows = [&]() {
 #pragma unroll
     for (int r = 0; r < R; ++r) {
@@ -650,16 +718,16 @@ NDPP_HD int mu_gauss_task(const FgBatch& B, int level, int base, int t) {
         if (l < B.L && (mask & chan_bit(r, l))) B.F(slot, r * B.L + l, n_node) = If[r * LMAX + l];
     }
   };
-  if (near && B.gl_graded > 0) {
+  if (p == kGaussPhGraded) {
     // next to the peak: the graded rule against itself with every panel halved
     gauss_graded<R, LMAX>(B, q, fv, a, b, B.gl_graded, 1, pk, Ic);
     gauss_graded<R, LMAX>(B, q, fv, a, b, B.gl_graded, 2, pk, If);
     evals += 3 * (B.gl_graded + 1) * kGaussN;
     take_agreeing_rows();
-    if (done == rows) {
-      B.t_gl[t] = (unsigned char)rows;
-      return evals;
-    }
+    if (done == rows) { finish(rows); return evals; }
+    c.st = near | rows | (done << kGaussDone);
+    next = kGaussPhLadder;
+    return evals;
   }
   gauss_composite<R, LMAX>(B, q, fv, a, b, 4, pk, Ic);
   evals += 4 * kGaussN;
@@ -671,8 +739,21 @@ NDPP_HD int mu_gauss_task(const FgBatch& B, int level, int base, int t) {
 #pragma unroll
     for (int k = 0; k < R * LMAX; ++k) Ic[k] = If[k];
   }
-  rows = done;
-  B.t_gl[t] = (unsigned char)rows;
+  finish(done);
+  return evals;
+}
+
+// One flagged inner integral on its own: its phases in turn.  Returns the kernel values evaluated.
+template <int R, int LMAX>
+NDPP_HD int mu_gauss_task(const FgBatch& B, int level, int base, int t) {
+  GaussCand c{t, mu_gauss_entry<R>(B, level, base, t)};
+  if (!c.st) return 0;
+  int evals = 0;
+  for (int p = gauss_next_phase(B, -1, c.st); p < kGaussPhases;) {
+    int next;
+    evals += mu_gauss_phase<R, LMAX>(B, level, base, p, c, next);
+    p = next;
+  }
   return evals;
 }
 #endif

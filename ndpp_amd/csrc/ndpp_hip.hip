@@ -687,7 +687,7 @@ int run_batch_d(const ndpp_params* p, double A, double kT, double cutoff, double
   } slot[kNumFgContexts];
   for (int k = 0; k < pl.contexts; ++k) {
     slot[k].lvl_cnt = cv.take<int>(kMaxLevels + 2);
-    slot[k].next_task = cv.take<int>(2 * (kMaxLevels + 2));     // one row of counters per order class
+    slot[k].next_task = cv.take<int>(2 * (kMaxLevels + 2));     // per level: the walk's, the Gauss stage's
     slot[k].overflow = cv.take<int>(64);
     slot[k].mu_nodes = cv.take<int>(64);
     slot[k].mask_hist = cv.take<int>(nb_sort);
@@ -700,6 +700,10 @@ int run_batch_d(const ndpp_params* p, double A, double kT, double cutoff, double
   const char* ng = getenv("NDPP_HIP_GAUSS");        // 0: every inner integral by the adaptive walk
   const bool gauss_on = NDPP_FAST && look_at_tables && !(ng && ng[0] == '0') &&
                         fg_gauss_box(p->adaptive_mu_its, p->adaptive_mu_tol);
+  // 0: the Gauss stage one candidate per lane (the previous kernel, kept for comparison); default:
+  // by phases, each run by a wave of candidates that have reached it (fg_gauss_phased_kernel)
+  const char* nph = getenv("NDPP_HIP_GAUSS_PHASED");
+  const bool gauss_phased = !(nph && nph[0] == '0');
   const char* nsort = getenv("NDPP_HIP_NO_SORT");   // test hook: walk tasks in creation order
   const bool do_sort = !(nsort && nsort[0] == '1');
 
@@ -957,7 +961,7 @@ int run_batch_d(const ndpp_params* p, double A, double kT, double cutoff, double
         HIP_TRY(hipEventCreate(&gb));
         c.gev.emplace_back(ga, gb);
         HIP_TRY(hipEventRecord(ga, s));
-        launch_gauss_any(B, level, s);
+        launch_gauss_any(B, level, g_ws.num_cu, gauss_phased, s);
         HIP_TRY(hipEventRecord(gb, s));
       }
       if (do_sort) {
