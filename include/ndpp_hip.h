@@ -508,6 +508,24 @@ void ndpp_free_scatt_result(ndpp_scatt_result *r);
 int  ndpp_scatt_library(const ndpp_params *p, int n_nuclides, const ndpp_ace_nuclide *nuclides,
                         int n_bins, const double *e_bins, int nuscatt, ndpp_scatt_result *out);
 
+/* ndpp_scatt_library at the caller's incoming energies: create_Ein_grid (scatt.F90:166-243) is
+ * replaced by the lists n_el[k] / ein_el[k] and n_inel[k] / ein_inel[k] of nuclide k; everything
+ * else -- init / convert_distro, the free-gas / file-4 routing per energy, the one mixed elastic
+ * batch, the reaction sum, nu-scatter, result ownership -- is the code of the call above.  Replaces
+ * nothing in the reference, which integrates on its own grids only; it is what lets a host ask
+ * what a row BETWEEN two grid points is (ndpp_grid_error).  Each list holds positive, finite
+ * energies that never decrease (equal neighbours pass: the built grids keep the duplicates of
+ * the tables they merge); an empty list (n = 0, pointer unread) gives an empty section.  An
+ * energy above the top group edge gets the copy of the row before it, as in the built grids;
+ * a list that STARTS above the top edge has no such row and is NDPP_EINVAL.
+ * Given the grids ndpp_scatt_library built -- or any subset of them -- the rows are the same
+ * bits.  Legendre moments only.  NDPP_EINVAL is decided before the device is touched.         */
+int  ndpp_scatt_library_at(const ndpp_params *p, int n_nuclides, const ndpp_ace_nuclide *nuclides,
+                           int n_bins, const double *e_bins, int nuscatt,
+                           const int *n_el, const double *const *ein_el,
+                           const int *n_inel, const double *const *ein_inel,
+                           ndpp_scatt_result *out);
+
 /* calc_scatt(..., scatt_type = tabular, ...): the two calls above with N = n_tab lab-cosine
  * bins per (E_in, group) instead of Legendre moments (see ndpp_elastic_tab_batch); same
  * incoming grids, same sigma * p_valid weighting and reaction sum, nu-scatter included.
@@ -643,6 +661,23 @@ int ndpp_scatt_positivity(int n_ein, int G, int L, const double *mat, int n_mome
  * moments[n_ein][L] (one group's, or condensed, moments per E_in).                        */
 int ndpp_expand_moments(int n_ein, int L, const double *moments, int n_moments,
                         int n_mu, const double *mu, double *out /* [n_ein][n_mu] */);
+
+/* ---- interpolation error of an incoming-energy grid.  Replaces nothing: the reference never
+ * measures it (thin_grid compares stored rows with each other, never with a fresh one).
+ * x[n] with rows y[n][G][L]; x_mid[n-1] with rows y_mid[n-1][G][L] integrated there.  For
+ * interval i, with f = ln(x_mid[i] / x[i]) / ln(x[i+1] / x[i]) (thin_grid's rule, thin.F90):
+ *   err[i] = max over (g,l) of | y[i] + (y[i+1] - y[i]) f - y_mid[i] | / scale_i,
+ *   scale_i = max over g of |P0| (l = 0) in the rows y[i], y[i+1], y_mid[i];
+ * err[i] = 0 when scale_i is 0.  arg[i] = g * L + l of the maximum, the lowest on a tie.
+ * An interval with x[i+1] <= x[i], with x_mid[i] outside (x[i], x[i+1]), or with an abscissa
+ * that is not positive and finite is skipped: err = -1, arg = -1.  A NaN or an infinity in the
+ * three rows (or produced by them) gives err = +inf and arg = the first such element.
+ * f comes from the host's log, the rest is + - * / and comparisons in that order without
+ * contraction, on the device: a host restatement reproduces err and arg bit for bit.
+ * NDPP_EINVAL: L < 1, G < 1, n < 2, a NULL pointer -- decided before the device is touched.   */
+int ndpp_grid_error(int L, int G, int n, const double *x, const double *y /* [n][G][L] */,
+                    const double *x_mid /* [n-1] */, const double *y_mid /* [n-1][G][L] */,
+                    double *err /* [n-1] */, int *arg /* [n-1] */);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,117 @@
+// grid_kernels.hip -- what interpolating between two neighbours of an incoming-energy grid costs:
+// the error of the interpolated row against a freshly integrated row at a point between them.
+// Nothing in the reference does this (thin_grid, thin.F90, compares stored rows with each other);
+// the interpolation rule is the one thin_grid assumes, linear in ln E (thin.hip):
+//   f      = ln(x_mid / x_i) / ln(x_{i+1} / x_i)
+//   d(g,l) = | y_i + (y_{i+1} - y_i) f - y_mid |
+//   err_i  = max d / max_g |P0| over the three rows          (0 when that scale is 0)
+//
+// f is computed on the host, once per interval, and uploaded: the kernel is + - * / fabs and
+// comparisons only, built without contraction, so a host restatement with the same operation
+// order gives the same bits (ndpp_amd/gridcheck.py: grid_error_numpy).
+//
+// One wave64 per interval, the grid strides over intervals.  The three rows are G*L contiguous
+// doubles each; the lanes stride over them (coalesced loads), each lane keeps its running
+// (value, index) maximum in ascending index order, one butterfly over the wave folds them with
+// "larger value, then lower index", and lane 0 writes the two results.  No LDS, no atomics.
+// Memory-bound: 3 * G * L * 8 bytes per interval.
+#include <climits>
+#include <cmath>
+#include <vector>
+
+#include "../../include/ndpp_hip.h"
+#include "dev_util.h"
+#include "kernels.h"
+
+namespace ndpp {
+namespace {
+
+constexpr int kThreads = 256;          // 4 waves = 4 intervals per block and pass
+
+__global__ void __launch_bounds__(kThreads)
+grid_error_kernel(int n_int, int GL, int L, const double* __restrict__ y, const double* __restrict__ y_mid,
+                  const double* __restrict__ f, double* __restrict__ err, int* __restrict__ arg) {
+  const int lane = threadIdx.x & 63;
+  const long wave = ((long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const long n_waves = ((long)gridDim.x * blockDim.x) >> 6;
+  for (long i = wave; i < n_int; i += n_waves) {          // wave-uniform trip count
+    const double fi = f[i];
+    if (fi < 0.0) {                                       // skipped interval (marked by the host)
+      if (lane == 0) { err[i] = -1.0; arg[i] = -1; }
+      continue;
+    }
+    const double* a = y + (size_t)i * GL;
+    const double* b = a + GL;
+    const double* m = y_mid + (size_t)i * GL;
+    double dmax = -1.0, scale = 0.0;
+    int imax = INT_MAX, ibad = INT_MAX;
+    for (int e = lane; e < GL; e += 64) {
+      const double ya = a[e], yb = b[e], ym = m[e];
+      const double d = fabs(ya + (yb - ya) * fi - ym);
+      if (!(d < INFINITY)) { if (e < ibad) ibad = e; }    // NaN or infinite
+      else if (d > dmax) { dmax = d; imax = e; }
+      if (e % L == 0) scale = fmax(scale, fmax(fabs(ya), fmax(fabs(yb), fabs(ym))));
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+      const double v = __shfl_xor(dmax, o);
+      const int k = __shfl_xor(imax, o);
+      if (v > dmax || (v == dmax && k < imax)) { dmax = v; imax = k; }
+      ibad = min(ibad, __shfl_xor(ibad, o));
+      scale = fmax(scale, __shfl_xor(scale, o));
+    }
+    if (lane == 0) {
+      if (ibad != INT_MAX) { err[i] = INFINITY; arg[i] = ibad; }
+      else { err[i] = scale == 0.0 ? 0.0 : dmax / scale; arg[i] = imax; }
+    }
+  }
+}
+
+#define GRID_TRY(expr)                                                            \
+  do {                                                                            \
+    hipError_t e_ = (expr);                                                       \
+    if (e_ != hipSuccess)                                                         \
+      return fail(NDPP_EDEVICE, "%s failed: %s", #expr, hipGetErrorString(e_));   \
+  } while (0)
+
+}  // namespace
+}  // namespace ndpp
+
+using namespace ndpp;
+
+extern "C" int ndpp_grid_error(int L, int G, int n, const double* x, const double* y, const double* x_mid,
+                               const double* y_mid, double* err, int* arg) {
+  if (L < 1 || G < 1 || n < 2) return fail(NDPP_EINVAL, "grid_error: L=%d G=%d n=%d (need L, G >= 1, n >= 2)", L, G, n);
+  if (!x || !y || !x_mid || !y_mid || !err || !arg) return fail(NDPP_EINVAL, "grid_error: NULL argument");
+  if ((long)G * L > INT_MAX / 2) return fail(NDPP_EINVAL, "grid_error: G * L = %ld does not fit an index", (long)G * L);
+  const int GL = G * L, n_int = n - 1;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
+    return fail(NDPP_EDEVICE, "no HIP device available (libndpp_hip has no CPU path)");
+
+  // f per interval; -1 marks the intervals that are skipped: abscissae that are not positive and
+  // finite, x[i+1] <= x[i], or x_mid outside (x[i], x[i+1])
+  std::vector<double> f((size_t)n_int);
+  for (int i = 0; i < n_int; ++i) {
+    const double x0 = x[i], x1 = x[i + 1], xm = x_mid[i];
+    const bool ok = std::isfinite(x0) && std::isfinite(x1) && x0 > 0.0 && x1 > x0 && xm > x0 && xm < x1;
+    f[i] = ok ? std::log(xm / x0) / std::log(x1 / x0) : -1.0;
+  }
+  DevBuf<double> d_y, d_mid, d_f, d_err;
+  DevBuf<int> d_arg;
+  GRID_TRY(d_y.upload(y, (size_t)n * GL));
+  GRID_TRY(d_mid.upload(y_mid, (size_t)n_int * GL));
+  GRID_TRY(d_f.upload(f.data(), f.size()));
+  GRID_TRY(d_err.alloc(n_int));
+  GRID_TRY(d_arg.alloc(n_int));
+  {
+    GpuSpan span(nullptr, -1);
+    hipLaunchKernelGGL(grid_error_kernel, dim3(nblk((long)n_int * 64, kThreads)), dim3(kThreads), 0, 0, n_int, GL, L,
+                       d_y.p, d_mid.p, d_f.p, d_err.p, d_arg.p);
+    span.end();
+    GRID_TRY(hipGetLastError());
+    GRID_TRY(hipDeviceSynchronize());
+  }
+  GRID_TRY(hipMemcpy(err, d_err.p, sizeof(double) * n_int, hipMemcpyDeviceToHost));
+  GRID_TRY(hipMemcpy(arg, d_arg.p, sizeof(int) * n_int, hipMemcpyDeviceToHost));
+  return NDPP_OK;
+}

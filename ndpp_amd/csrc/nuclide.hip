@@ -211,6 +211,13 @@ struct ElasticDefer {
   int n_rows = 0;
 };
 
+// Where the two incoming grids of a nuclide come from: create_Ein_grid (no GivenGrids), or the
+// caller's own lists (ndpp_scatt_library_at).  Everything after the grids is the same code.
+struct GivenGrids {
+  int n_el, n_inel;
+  const double *ein_el, *ein_inel;
+};
+
 // the parts of a Reaction that ScattData%init may rewrite (:160-223)
 struct RxnState {
   bool has_angle_dist;
@@ -234,7 +241,7 @@ extern "C" void ndpp_free_scatt_result(ndpp_scatt_result* r) {
 // n_tab lab-cosine bins per group (the tabular batch calls; no deferred or level batches)
 static int scatt_nuclide_impl(const ndpp_params* p, const ndpp_ace_nuclide* nuc, int n_bins,
                               const double* e_bins, int nuscatt, ndpp_scatt_result* out,
-                              ElasticDefer* defer, int n_tab = 0) {
+                              ElasticDefer* defer, int n_tab = 0, const GivenGrids* given = nullptr) {
   if (!p || !nuc || !e_bins || !out) return fail(NDPP_EINVAL, "NULL argument");
   memset(out, 0, sizeof(*out));
   if (n_tab < 0 || n_tab > NDPP_MAX_TAB_BINS)
@@ -354,7 +361,7 @@ static int scatt_nuclide_impl(const ndpp_params* p, const ndpp_ace_nuclide* nuc,
   }
   if (!any) return fail(NDPP_EINVAL, "no scattering reaction in this nuclide");
 
-  // ---- incoming grids (:134-135)
+  // ---- incoming grids (:134-135), or the caller's
   std::vector<ndpp_sd_grid> gs(sds.size());
   for (size_t k = 0; k < sds.size(); ++k) {
     gs[k].is_init = sds[k].is_init;
@@ -364,15 +371,21 @@ static int scatt_nuclide_impl(const ndpp_params* p, const ndpp_ace_nuclide* nuc,
     gs[k].e_grid = sds[k].e_grid.data();
   }
   int n_el = 0, n_in = 0;
-  rc = ndpp_create_ein_grid(p, (int)gs.size(), gs.data(), n_bins, e_bins, nuc->n_grid, nuc->energy,
-                            nuc->awr, nuc->kT, cutoff, inel_thresh, 0, nullptr, &n_el, 0, nullptr,
-                            &n_in);
-  if (rc) return rc;
+  if (given) {
+    n_el = given->n_el;
+    n_in = given->n_inel;
+  } else {
+    rc = ndpp_create_ein_grid(p, (int)gs.size(), gs.data(), n_bins, e_bins, nuc->n_grid, nuc->energy,
+                              nuc->awr, nuc->kT, cutoff, inel_thresh, 0, nullptr, &n_el, 0, nullptr,
+                              &n_in);
+    if (rc) return rc;
+  }
   out->L = L; out->G = G; out->n_el = n_el; out->n_inel = n_in;
   const size_t GL = (size_t)G * L;
   hc.lap(0);
-  out->ein_el = (double*)calloc((size_t)n_el, sizeof(double));
-  out->el_mat = (double*)calloc((size_t)n_el * GL, sizeof(double));
+  // (an empty given list still gets its one-element arrays: a NULL here means out of memory)
+  out->ein_el = (double*)calloc(std::max<size_t>((size_t)n_el, 1), sizeof(double));
+  out->el_mat = (double*)calloc(std::max<size_t>((size_t)n_el * GL, 1), sizeof(double));
   if (n_in) {
     out->ein_inel = (double*)calloc((size_t)n_in, sizeof(double));
     // (overwritten as a whole by the download of the device-side reaction sum)
@@ -384,10 +397,15 @@ static int scatt_nuclide_impl(const ndpp_params* p, const ndpp_ace_nuclide* nuc,
     ndpp_free_scatt_result(out);
     return fail(NDPP_ENOMEM, "out of host memory for the result matrices");
   }
-  rc = ndpp_create_ein_grid(p, (int)gs.size(), gs.data(), n_bins, e_bins, nuc->n_grid, nuc->energy,
-                            nuc->awr, nuc->kT, cutoff, inel_thresh, n_el, out->ein_el, &n_el,
-                            std::max(n_in, 0), out->ein_inel, &n_in);
-  if (rc) { ndpp_free_scatt_result(out); return rc; }
+  if (given) {
+    std::copy(given->ein_el, given->ein_el + n_el, out->ein_el);
+    if (n_in) std::copy(given->ein_inel, given->ein_inel + n_in, out->ein_inel);
+  } else {
+    rc = ndpp_create_ein_grid(p, (int)gs.size(), gs.data(), n_bins, e_bins, nuc->n_grid, nuc->energy,
+                              nuc->awr, nuc->kT, cutoff, inel_thresh, n_el, out->ein_el, &n_el,
+                              std::max(n_in, 0), out->ein_inel, &n_in);
+    if (rc) { ndpp_free_scatt_result(out); return rc; }
+  }
 
   hc.lap(1);
   // ---- the two grids
@@ -622,9 +640,11 @@ extern "C" int ndpp_scatt_nuclide(const ndpp_params* p, const ndpp_ace_nuclide* 
   return scatt_nuclide_impl(p, nuc, n_bins, e_bins, nuscatt, out, nullptr);
 }
 
-extern "C" int ndpp_scatt_library(const ndpp_params* p, int n_nuclides,
-                                  const ndpp_ace_nuclide* nuclides, int n_bins,
-                                  const double* e_bins, int nuscatt, ndpp_scatt_result* out) {
+// calc_scatt for a list of nuclides, their elastic grids in ONE mixed batch.  grids: null (every
+// nuclide builds its own, ndpp_scatt_library) or one GivenGrids per nuclide (ndpp_scatt_library_at).
+static int scatt_library_impl(const ndpp_params* p, int n_nuclides, const ndpp_ace_nuclide* nuclides,
+                              int n_bins, const double* e_bins, int nuscatt, const GivenGrids* grids,
+                              ndpp_scatt_result* out) {
   if (n_nuclides < 0 || (n_nuclides > 0 && (!nuclides || !out)))
     return fail(NDPP_EINVAL, "n_nuclides=%d or NULL array", n_nuclides);
   for (int k = 0; k < n_nuclides; ++k) memset(&out[k], 0, sizeof(out[k]));
@@ -655,13 +675,56 @@ extern "C" int ndpp_scatt_library(const ndpp_params* p, int n_nuclides,
   };
   constexpr size_t kFlushBytes = (size_t)3 << 30;
   for (int k = 0; k < n_nuclides && rc == NDPP_OK; ++k) {
-    rc = scatt_nuclide_impl(p, &nuclides[k], n_bins, e_bins, nuscatt, &out[k], &d);
+    rc = scatt_nuclide_impl(p, &nuclides[k], n_bins, e_bins, nuscatt, &out[k], &d, 0, grids ? &grids[k] : nullptr);
     if (rc == NDPP_OK && d.f_tab.size() * sizeof(double) > kFlushBytes) rc = flush();
   }
   if (rc == NDPP_OK) rc = flush();
   if (rc != NDPP_OK)
     for (int k = 0; k < n_nuclides; ++k) ndpp_free_scatt_result(&out[k]);
   return rc;
+}
+
+extern "C" int ndpp_scatt_library(const ndpp_params* p, int n_nuclides,
+                                  const ndpp_ace_nuclide* nuclides, int n_bins,
+                                  const double* e_bins, int nuscatt, ndpp_scatt_result* out) {
+  return scatt_library_impl(p, n_nuclides, nuclides, n_bins, e_bins, nuscatt, nullptr, out);
+}
+
+// a caller's list of incoming energies: positive, finite, never decreasing (the grids
+// create_Ein_grid builds keep the duplicates of the tables they merge, so equal neighbours pass)
+static int check_given_list(const char* what, int k, int n, const double* e, double Etop) {
+  if (n < 0) return fail(NDPP_EINVAL, "scatt_library_at: nuclide %d: %s list of %d energies", k, what, n);
+  if (n > 0 && !e) return fail(NDPP_EINVAL, "scatt_library_at: nuclide %d: NULL %s list", k, what);
+  // an energy above the top group edge takes the row before it: there must be one
+  if (n > 0 && e[0] > Etop)
+    return fail(NDPP_EINVAL, "scatt_library_at: nuclide %d: the first %s energy %g is above the top group edge %g", k, what, e[0], Etop);
+  for (int i = 0; i < n; ++i) {
+    if (!std::isfinite(e[i]) || !(e[i] > 0.0))
+      return fail(NDPP_EINVAL, "scatt_library_at: nuclide %d: %s energy %d = %g is not positive and finite", k, what, i, e[i]);
+    if (i > 0 && e[i] < e[i - 1])
+      return fail(NDPP_EINVAL, "scatt_library_at: nuclide %d: %s energies decrease at %d", k, what, i);
+  }
+  return NDPP_OK;
+}
+
+extern "C" int ndpp_scatt_library_at(const ndpp_params* p, int n_nuclides, const ndpp_ace_nuclide* nuclides,
+                                     int n_bins, const double* e_bins, int nuscatt, const int* n_el,
+                                     const double* const* ein_el, const int* n_inel,
+                                     const double* const* ein_inel, ndpp_scatt_result* out) {
+  if (n_nuclides > 0 && out)
+    for (int k = 0; k < n_nuclides; ++k) memset(&out[k], 0, sizeof(out[k]));
+  if (!p || !e_bins) return fail(NDPP_EINVAL, "scatt_library_at: NULL argument");
+  if (n_nuclides < 0 || (n_nuclides > 0 && (!nuclides || !out || !n_el || !ein_el || !n_inel || !ein_inel)))
+    return fail(NDPP_EINVAL, "scatt_library_at: n_nuclides=%d or NULL array", n_nuclides);
+  if (n_bins < 2) return fail(NDPP_EINVAL, "need at least one group");
+  std::vector<GivenGrids> grids((size_t)std::max(n_nuclides, 0));
+  for (int k = 0; k < n_nuclides; ++k) {
+    int rc = check_given_list("elastic", k, n_el[k], ein_el[k], e_bins[n_bins - 1]);
+    if (rc == NDPP_OK) rc = check_given_list("inelastic", k, n_inel[k], ein_inel[k], e_bins[n_bins - 1]);
+    if (rc) return rc;
+    grids[k] = GivenGrids{n_el[k], n_inel[k], ein_el[k], ein_inel[k]};
+  }
+  return scatt_library_impl(p, n_nuclides, nuclides, n_bins, e_bins, nuscatt, grids.data(), out);
 }
 
 extern "C" int ndpp_scatt_nuclide_tab(const ndpp_params* p, int n_tab, const ndpp_ace_nuclide* nuc, int n_bins,

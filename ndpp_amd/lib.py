@@ -45,7 +45,7 @@ EXPORTS = [
     "ndpp_lib_xml_nuclide", "ndpp_lib_xml_closer", "ndpp_finish_scatt", "ndpp_nuclide_file",
     "ndpp_scatt_positivity", "ndpp_expand_moments",
     "ndpp_elastic_tab_batch", "ndpp_file6_tab_batch", "ndpp_law9_tab_batch", "ndpp_scatt_nuclide_tab",
-    "ndpp_scatt_library_tab",
+    "ndpp_scatt_library_tab", "ndpp_scatt_library_at", "ndpp_grid_error",
 ]
 
 
@@ -580,6 +580,12 @@ def load(build_if_missing: bool = False, torch_compat: bool | None = None) -> C.
     lib.ndpp_law9_tab_batch.argtypes = [PP, C.c_int] + lib.ndpp_law9_leg_batch.argtypes[1:]
     lib.ndpp_scatt_nuclide_tab.argtypes = [PP, C.c_int] + lib.ndpp_scatt_nuclide.argtypes[1:]
     lib.ndpp_scatt_library_tab.argtypes = [PP, C.c_int] + lib.ndpp_scatt_library.argtypes[1:]
+    if not explicit:
+        c_double_pp = C.POINTER(c_double_p)
+        lib.ndpp_scatt_library_at.argtypes = [PP, C.c_int, C.POINTER(AceNuclide), C.c_int, c_double_p, C.c_int,
+                                              c_int_p, c_double_pp, c_int_p, c_double_pp, C.POINTER(ScattResult)]
+        lib.ndpp_grid_error.argtypes = [C.c_int, C.c_int, C.c_int, c_double_p, c_double_p, c_double_p, c_double_p,
+                                        c_double_p, c_int_p]
     _lib = lib
     return lib
 
@@ -898,7 +904,8 @@ def create_ein_grid(params: Params, sds, e_bins, nuc_grid, awr, kT, cutoff, thre
 
 def _scatt_result_dict(r):
     G, L = r.G, r.L
-    arr = lambda ptr, shape: np.ctypeslib.as_array(ptr, shape=shape).copy() if ptr else None
+    arr = lambda ptr, shape: ((np.ctypeslib.as_array(ptr, shape=shape).copy() if shape[0] else np.zeros(shape))
+                              if ptr else None)
     return dict(ein_el=arr(r.ein_el, (r.n_el,)), el_mat=arr(r.el_mat, (r.n_el, G, L)),
                 ein_inel=arr(r.ein_inel, (r.n_inel,)) if r.n_inel else None,
                 inel_mat=arr(r.inel_mat, (r.n_inel, G, L)) if r.n_inel else None,
@@ -921,6 +928,46 @@ def scatt_library(params: Params, nuclides, e_bins, nuscatt: bool = True):
     finally:
         for k in range(len(nucs)):
             load().ndpp_free_scatt_result(C.byref(res[k]))
+
+
+def scatt_library_at(params: Params, nuclides, e_bins, ein_el, ein_inel, nuscatt: bool = True):
+    """ndpp_scatt_library_at: scatt_library at the caller's incoming energies.  ein_el[k] /
+    ein_inel[k]: the elastic and inelastic energies of nuclide k (None or empty: none; an
+    empty inelastic list gives ein_inel = inel_mat = None, as for an elastic-only nuclide).
+    Returns a list of result dicts like scatt_library's."""
+    nucs = [n if isinstance(n, AceNuclide) else AceNuclide.from_desc(n) for n in nuclides]
+    if len(ein_el) != len(nucs) or len(ein_inel) != len(nucs):
+        raise ValueError("one elastic and one inelastic list per nuclide")
+    arr = (AceNuclide * max(len(nucs), 1))()
+    for k, n in enumerate(nucs):
+        C.memmove(C.byref(arr[k]), C.byref(n), C.sizeof(AceNuclide))
+    e_bins = _f64(e_bins)
+    lists = [[_f64(np.zeros(0) if e is None else e) for e in side] for side in (ein_el, ein_inel)]
+    cnt = [np.array([len(e) for e in side] + [0], dtype=np.int32) for side in lists]
+    ptr = [(c_double_p * max(len(nucs), 1))(*[_dp(e) for e in side]) for side in lists]
+    res = (ScattResult * max(len(nucs), 1))()
+    _check(load().ndpp_scatt_library_at(C.byref(params), len(nucs), arr, len(e_bins), _dp(e_bins),
+                                        int(bool(nuscatt)), _ip(cnt[0]), ptr[0], _ip(cnt[1]), ptr[1], res))
+    try:
+        return [_scatt_result_dict(res[k]) for k in range(len(nucs))]
+    finally:
+        for k in range(len(nucs)):
+            load().ndpp_free_scatt_result(C.byref(res[k]))
+
+
+def grid_error(x, y, x_mid, y_mid):
+    """ndpp_grid_error: per interval of x[n] the error of log-interpolating between the rows
+    y[i], y[i+1] (y[n][G][L]) against the row y_mid[i] integrated at x_mid[i], over the rows'
+    P0 scale (include/ndpp_hip.h).  Returns (err[n-1], arg[n-1]); err -1: skipped, inf: not finite."""
+    x, y, x_mid, y_mid = _f64(x), _f64(y), _f64(x_mid), _f64(y_mid)
+    if y.ndim != 3 or y_mid.ndim != 3:
+        raise ValueError(f"y and y_mid must be (n, G, L), got {y.shape} and {y_mid.shape}")
+    n, G, L = y.shape
+    if len(x) != n or len(x_mid) != n - 1 or y_mid.shape != (n - 1, G, L):
+        raise ValueError(f"shapes do not match: x {x.shape}, y {y.shape}, x_mid {x_mid.shape}, y_mid {y_mid.shape}")
+    err, arg = np.zeros(max(n - 1, 0)), np.zeros(max(n - 1, 0), dtype=np.int32)
+    _check(load().ndpp_grid_error(L, G, n, _dp(x), _dp(y), _dp(x_mid), _dp(y_mid), _dp(err), _ip(arg)))
+    return err, arg
 
 
 def scatt_nuclide(params: Params, nuclide, e_bins, nuscatt: bool = True):

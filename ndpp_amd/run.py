@@ -17,7 +17,24 @@ computed (ndpp_nuclide_file does not write it).
 Exit status: 0 library written, 2 input error (nothing written), 3 library or device error
 (nothing written).  Files are written under temporary names and renamed once every table is
 done, so a failed run leaves no partial library.
---json FILE: one record per table (kind, incoming energies, wall time, device time)."""
+--json FILE: one record per table (kind, incoming energies, wall time, device time).
+
+Grid quality (ndpp_amd.gridcheck; Legendre output only, scatt_type tabular with either flag is an
+input error):
+  --check-grid         once every table is computed, and before anything is written, integrate
+                       every table at the midpoints of its incoming grids; the files written are
+                       those of a run without the flag.  Prints, per table and section, the worst
+                       error of interpolating between grid points; the report goes under "grid" in
+                       --json.  The exit status does not depend on what the check finds (a device
+                       error during the check is a library error like any other: exit 3, nothing
+                       written).
+  --refine-grid TOL    before print_tol / thinning / writing, insert midpoint rows into the grids
+                       of the neutron tables until no interval's error is above TOL
+                       (--max-passes N, default 6; --max-growth X, default 4); what stays above
+                       TOL is reported as unresolved.  With --check-grid the refined grids are
+                       what is checked.
+  --check-tol X        the tolerance --check-grid counts intervals against (default: TOL of
+                       --refine-grid, else 1e-3); an input error without --check-grid."""
 from __future__ import annotations
 
 import argparse
@@ -31,7 +48,7 @@ from pathlib import Path
 
 import numpy as np
 
-from . import ace, grid, lib
+from . import ace, grid, gridcheck, lib
 
 EXIT_OK, EXIT_INPUT, EXIT_LIBRARY = 0, 2, 3
 
@@ -262,11 +279,15 @@ def _device_ms() -> float:
     return float(sum(lib.profile_get().values()))
 
 
-def compute(s: dict, tables: list) -> tuple:
-    """Every table's file bytes and its timing record: ([(file name, bytes)], [record])."""
+def compute(s: dict, tables: list, grid_opts: dict | None = None) -> tuple:
+    """Every table's file bytes, its timing record and the grid report: ([(file name, bytes)],
+    [record], report).  The report is None without grid_opts (check, check_tol, refine_tol,
+    max_passes, max_growth)."""
     p, o, bins = params_of(s), options_of(s), s["energy_bins"]
     tab = s["scatt_type"] == "tabular"
     files, recs = [None] * len(tables), [None] * len(tables)
+    go = grid_opts or {}
+    raw, grid_rep = [None] * len(tables), None
     neut = [k for k, t in enumerate(tables) if t["kind"] == "neutron"]
     if neut:
         lib.profile_reset()
@@ -276,7 +297,19 @@ def compute(s: dict, tables: list) -> tuple:
                lib.scatt_library(p, nucs, bins, s["nuscatter"]))
         wall, dev, last = time.perf_counter() - t0, _device_ms(), float(lib.load().ndpp_last_gpu_ms())
         call = "scatt_library_tab" if tab else "scatt_library"
+        if go.get("refine_tol") is not None:
+            t1 = time.perf_counter()
+            res, rep = gridcheck.refine(p, bins, [tables[k] for k in neut], res, s["nuscatter"], go["refine_tol"],
+                                        go["max_passes"], go["max_growth"])
+            # one record per table of the run, in listing order: the thermal ones say that they are not refined
+            by_table = dict(zip(neut, rep))
+            rep = [by_table.get(k) or dict(name=t["listing"]["name"], kind=t["kind"], grids={},
+                                           note="thermal table: checked, not refined")
+                   for k, t in enumerate(tables)]
+            grid_rep = dict(refine=dict(tol=go["refine_tol"], max_passes=go["max_passes"],
+                                        max_growth=go["max_growth"], wall_s=time.perf_counter() - t1, tables=rep))
         for k, r in zip(neut, res):
+            raw[k] = r
             t = tables[k]
             chi, chi_rec = None, None
             if s["integrate_chi"] and t["data"]["fissionable"]:
@@ -305,13 +338,19 @@ def compute(s: dict, tables: list) -> tuple:
         ein = grid.add_one_more_point(lib.sab_egrid_lib(p, d, bins))
         mat = lib.sab_batch(p, d, ein, bins)
         wall, dev, last = time.perf_counter() - t0, _device_ms(), float(lib.load().ndpp_last_gpu_ms())
+        raw[k] = dict(ein_el=ein, el_mat=mat, ein_inel=None, inel_mat=None, nuinel_mat=None)
         fin, _ = lib.finish_scatt(o, dict(ein_el=ein, el_mat=mat, ein_inel=None, inel_mat=None, nuinel_mat=None),
                                   bins)
         if s["lib_format"] != lib.FMT_NONE:
             files[k] = lib.nuclide_file(o, d["name"], d["kT"], fin, bins, is_sab=True)
         recs[k] = dict(name=t["listing"]["name"], kind="thermal", file=t["file"],
                        energies=dict(elastic=len(ein), inelastic=0), wall_s=wall, device_ms=dev, last_gpu_ms=last)
-    return [(t["file"], f) for t, f in zip(tables, files)], recs
+    out = [(t["file"], f) for t, f in zip(tables, files)]
+    if go.get("check"):
+        t1 = time.perf_counter()
+        rep = gridcheck.check(p, bins, tables, raw, s["nuscatter"], go["check_tol"])
+        grid_rep = dict(grid_rep or {}, check=dict(tol=go["check_tol"], wall_s=time.perf_counter() - t1, tables=rep))
+    return out, recs, grid_rep
 
 
 def lib_xml_of(s: dict, run_dir, tables: list) -> bytes:
@@ -364,12 +403,16 @@ def write_library(run_dir, files: list, xml: bytes) -> list:
     return [p for p, _ in items]
 
 
-def run(run_dir, json_path=None, out=sys.stdout) -> int:
+def run(run_dir, json_path=None, out=sys.stdout, grid_opts: dict | None = None) -> int:
     """The whole driver; returns the exit status."""
     run_dir = Path(run_dir)
     t_start = time.perf_counter()
     try:
         s = read_ndpp_xml(run_dir)
+        if grid_opts is not None and s["scatt_type"] == "tabular":
+            raise InputError("--check-grid and --refine-grid cover Legendre output only: the tabular rows of the "
+                             "free-gas range do not settle, so an error measured on them would be the "
+                             "quadrature's, not the grid's.")
         xs = read_cross_sections(s["cross_sections"])
         tables = load_tables(s, xs)
         if not tables:
@@ -384,7 +427,7 @@ def run(run_dir, json_path=None, out=sys.stdout) -> int:
         except InputError as e:
             print(f"ndpp_amd.run: input error: {e}", file=sys.stderr)
             return EXIT_INPUT
-        files, recs = compute(s, tables)
+        files, recs, grid_rep = compute(s, tables, grid_opts)
         xml = lib_xml_of(s, run_dir, tables)
     except (lib.NdppError, RuntimeError, OSError) as e:
         print(f"ndpp_amd.run: library error: {e}", file=sys.stderr)
@@ -399,10 +442,47 @@ def run(run_dir, json_path=None, out=sys.stdout) -> int:
         print(f"{r['name']:>12s} {r['kind']:8s} {r['energies']['elastic']:7d} + {r['energies']['inelastic']:6d} E_in"
               f"  -> {r['file']}", file=out)
     print(f"{len(tables)} tables, {len(written)} files written in {total:.2f} s", file=out)
+    if grid_rep and "refine" in grid_rep:
+        for t in grid_rep["refine"]["tables"]:
+            for name, g in t["grids"].items():
+                print(f"{t['name']:>12s} {name:13s} refined to {grid_rep['refine']['tol']:g}: {g['points_before']} -> "
+                      f"{g['points_after']} E_in in {g['passes']} passes ({g['stopped']}), {len(g['unresolved'])} "
+                      f"unresolved ({sum(u['at_breakpoint'] for u in g['unresolved'])} at a breakpoint)", file=out)
+    if grid_rep and "check" in grid_rep:
+        for line in gridcheck.format_lines(grid_rep["check"]["tables"]):
+            print(line, file=out)
     if json_path:
-        Path(json_path).write_text(json.dumps(dict(run_dir=str(run_dir), wall_s=total, scatt_type=s["scatt_type"],
-                                                   tables=recs), indent=1) + "\n")
+        rec = dict(run_dir=str(run_dir), wall_s=total, scatt_type=s["scatt_type"], tables=recs)
+        if grid_opts is not None:
+            rec["grid"] = grid_rep
+        Path(json_path).write_text(json.dumps(rec, indent=1) + "\n")
     return EXIT_OK
+
+
+def _grid_options(a):
+    """The grid flags as compute()'s grid_opts (None: no flag given).  Raises InputError."""
+    if a.check_tol is not None and not a.check_grid:
+        raise InputError("--check-tol is the tolerance of --check-grid: give both")
+    if not a.check_grid and a.refine_grid is None:
+        return None
+
+    def positive(flag, text):
+        try:
+            v = float(text)
+        except ValueError:
+            raise InputError(f"{flag} {text!r} is not a number") from None
+        if not (v > 0.0) or not math.isfinite(v):
+            raise InputError(f"{flag} {text!r}: a positive, finite number is expected")
+        return v
+
+    tol = None if a.refine_grid is None else positive("--refine-grid", a.refine_grid)
+    ctol = positive("--check-tol", a.check_tol) if a.check_tol is not None else (tol if tol is not None else 1.0e-3)
+    if a.max_passes < 0:
+        raise InputError(f"--max-passes {a.max_passes}: must not be negative")
+    if not (a.max_growth >= 1.0):
+        raise InputError(f"--max-growth {a.max_growth}: must be at least 1")
+    return dict(check=bool(a.check_grid), check_tol=ctol, refine_tol=tol, max_passes=a.max_passes,
+                max_growth=a.max_growth)
 
 
 def main(argv=None) -> int:
@@ -412,8 +492,22 @@ def main(argv=None) -> int:
                                              "3: library or device error; nothing is written on failure).")
     ap.add_argument("run_dir", help="directory holding ndpp.xml; the library is written there")
     ap.add_argument("--json", default=None, help="write per-table timings to this file")
+    ap.add_argument("--check-grid", action="store_true",
+                    help="measure the interpolation error of every incoming-energy grid against midpoint integrals")
+    ap.add_argument("--refine-grid", metavar="TOL", default=None,
+                    help="insert midpoint rows into the neutron tables' grids until that error is below TOL")
+    ap.add_argument("--max-passes", type=int, default=6, help="refinement passes at most (default 6)")
+    ap.add_argument("--max-growth", type=float, default=4.0,
+                    help="a grid stops refining before it exceeds this multiple of its length (default 4)")
+    ap.add_argument("--check-tol", metavar="X", default=None,
+                    help="tolerance --check-grid counts intervals against (default: TOL, else 1e-3)")
     a = ap.parse_args(argv)
-    return run(a.run_dir, a.json)
+    try:
+        grid_opts = _grid_options(a)
+    except InputError as e:
+        print(f"ndpp_amd.run: input error: {e}", file=sys.stderr)
+        return EXIT_INPUT
+    return run(a.run_dir, a.json, grid_opts=grid_opts)
 
 
 if __name__ == "__main__":
