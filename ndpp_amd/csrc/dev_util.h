@@ -118,7 +118,7 @@ inline hipError_t dev_alloc(void** p, size_t bytes) { return DevCache::get().all
 inline void dev_free(void* p) { DevCache::get().release(p); }
 inline void dev_cache_trim() { DevCache::get().trim(); }
 
-// owning device buffer; upload() = allocate + copy from the host
+// owning device buffer; upload() = allocate + copy from the host (h null: allocate only), download() = copy back
 template <class T>
 struct DevBuf {
   T* p = nullptr;
@@ -132,6 +132,7 @@ struct DevBuf {
     if (e != hipSuccess) return e;
     return (n && h) ? hipMemcpy(p, h, n * sizeof(T), hipMemcpyHostToDevice) : hipSuccess;
   }
+  hipError_t download(T* h, size_t n) const { return hipMemcpy(h, p, n * sizeof(T), hipMemcpyDeviceToHost); }
 };
 
 }  // namespace ndpp

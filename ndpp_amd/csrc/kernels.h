@@ -39,18 +39,23 @@ void launch_file4_any(int n, const int* list, int mu_bins, const double* ein,
                       const int* nuc_of_ein = nullptr, const double* nuc_awr = nullptr,
                       const double* nuc_Q = nullptr);
 
-// fg_strict_stages.hip (always -DNDPP_FAST=0 -ffp-contract=off): the stages of the free-gas
-// pipeline in the reference's arithmetic.  `batch` points to the caller's FgBatch (same
-// layout in both arithmetic namespaces).
-int launch_fg_setup_strict(const void* batch, size_t batch_bytes, hipStream_t s);
-int launch_fg_prep_strict(const void* batch, size_t batch_bytes, int level, hipStream_t s);
-int launch_fg_mu_strict(const void* batch, size_t batch_bytes, int level, int num_cu,
-                        double* gstack, int* counter, hipStream_t s);
-int launch_fg_seg_zero_strict(const void* batch, size_t batch_bytes, int level, hipStream_t s);
-int launch_fg_combine_strict(const void* batch, size_t batch_bytes, int level, hipStream_t s);
-int launch_fg_node_strict(const void* batch, size_t batch_bytes, int level, hipStream_t s);
-int launch_fg_reduce_strict(const void* batch, size_t batch_bytes, int level, hipStream_t s);
-int launch_fg_assemble_strict(const void* batch, size_t batch_bytes, hipStream_t s);
+// One launcher per stage of the free-gas pipeline, in one arithmetic.  `batch` points to the
+// caller's FgBatch (same layout in both arithmetic namespaces) and `bytes` is its size there; an
+// entry returns NDPP_OK or what fail() returned.  The pipeline driver (ndpp_hip.hip) holds one
+// table per arithmetic and a context calls through the table of its own.
+struct FgStages {
+  int (*setup)(const void* batch, size_t bytes, hipStream_t s);
+  int (*prep)(const void* batch, size_t bytes, int level, hipStream_t s);
+  int (*seg_zero)(const void* batch, size_t bytes, int level, hipStream_t s);
+  int (*mu)(const void* batch, size_t bytes, int level, int num_cu, double* gstack, int* counter, hipStream_t s);
+  int (*combine)(const void* batch, size_t bytes, int level, hipStream_t s);
+  int (*node)(const void* batch, size_t bytes, int level, hipStream_t s);
+  int (*reduce)(const void* batch, size_t bytes, int level, hipStream_t s);
+  int (*assemble)(const void* batch, size_t bytes, hipStream_t s);
+};
+// fg_strict_stages.hip (always -DNDPP_FAST=0 -ffp-contract=off): the stages in the reference's
+// arithmetic.
+const FgStages& fg_strict_stages();
 
 // Where a batch call leaves its moments when the caller goes on working on the device (the
 // nuclide driver's reaction sum): consume() is handed the device array [n][G*L] instead of the

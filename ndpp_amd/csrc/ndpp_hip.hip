@@ -205,11 +205,11 @@ __global__ void classify_kernel(int n_ein, const double* ein, double cutoff,
   }
 }
 
+__global__ void fg_set_int_kernel(int* dst, int v) { *dst = v; }
+
 // Jobs of one chunk.  rows_per_job = R: job j integrates rows row_lo..row_lo+R-1 of
 // incoming energy list[j] jointly; with joint = 0 every (energy, row) pair is its
 // own single-row job (calls keep the order energy-major, row-minor either way).
-__global__ void fg_set_int_kernel(int* dst, int v) { *dst = v; }
-
 // (the k-th incoming energy of the chunk is list[k * lstride]: a list dealt round-robin to two
 // contexts is walked with stride 2)
 __global__ void make_jobs_kernel(int n_jobs, int rows_per_ein, int joint, const int* list, int lstride,
@@ -372,6 +372,11 @@ struct Workspace {
 constexpr int kMaxDevices = 64;
 Workspace g_ws_of[kMaxDevices];
 
+int require_device() {
+  if (ndpp_device_count() > 0) return NDPP_OK;
+  return fail(NDPP_EDEVICE, "no HIP device available (libndpp_hip has no CPU path)");
+}
+
 // the calling thread's current device and its workspace
 int current_workspace(Workspace** ws) {
   int dev = 0;
@@ -506,6 +511,7 @@ struct NucArrays {
 constexpr double kStrictBelowDefault = 0.0;      // x A kT
 constexpr double kStrictColdDefault = 1e-4;      // x kT
 constexpr double kStrictRoughDefault = 1e-12;    // x the row's largest |f|
+
 void arithmetic_switch(int G, double& strict_x, double& strict_cold, double& rough_rho) {
   strict_x = 0.0;
   strict_cold = 0.0;
@@ -528,37 +534,78 @@ void arithmetic_switch(int G, double& strict_x, double& strict_cold, double& rou
 #endif
 }
 
+// Every NDPP_HIP_* hook of the free-gas driver (named here without that prefix).  read_fg_tunables alone reads
+// them (the arithmetic switch's four through arithmetic_switch), per batch call: tests flip them between calls.
+struct FgTunables {
+  double strict_x, strict_cold, rough_rho;   // the arithmetic switch
+  bool joint = true;           // NO_JOINT=1: off.  Both bracketing rows of an incoming energy as one union tree
+  long nodes_per_call = 0;     // NODES_PER_CALL > 0: the arena guess per call, without spare room (test hook:
+  long max_chunk_ein = 0;      // forces overflow -> halve the chunk).  MAX_CHUNK_EIN > 0: caps a chunk (test hook)
+  bool split = true;           // NO_SPLIT=1: off.  The split walk (fg_pipeline.h kSplitLog2) on small levels ...
+  double split_x = 32.0;       // SPLIT_BELOW_X: ... those with at most this many inner integrals per lane
+  bool gauss = true;           // GAUSS=0: off, every inner integral goes to the adaptive walk
+  bool gauss_phased = true;    // GAUSS_PHASED=0: the Gauss stage one candidate per lane, not by phases
+  bool sort = true;            // NO_SORT=1: off, the walk takes a level's tasks in creation order (test hook)
+  long two_min = kTwoContextsMinEin, two_max = kTwoContextsMaxEin;   // TWO_CONTEXTS_MIN (0: one at a time), _MAX
+  // GAUSS_RATIO, _NEAR, _AMIN, _DEPTH, _DEPTH_NEAR, _GRADED, _PANELS: the fields of that name (experiment knobs;
+  // FgBatch's defaults are what profiles/r04/parity_tail_*.log were measured with), clamped as below
+  double gl_ratio, gl_amin;
+  int gl_near, gl_cert_depth, gl_cert_depth_near, gl_graded, gl_panels;
+};
+
+FgTunables read_fg_tunables(int G) {
+  FgTunables t;
+  arithmetic_switch(G, t.strict_x, t.strict_cold, t.rough_rho);
+  auto first_is = [](const char* name, char c) { const char* v = getenv(name); return v && v[0] == c; };
+  const char* e;
+  t.joint = !first_is("NDPP_HIP_NO_JOINT", '1');
+  if ((e = getenv("NDPP_HIP_NODES_PER_CALL")) && atol(e) > 0) t.nodes_per_call = atol(e);
+  if ((e = getenv("NDPP_HIP_MAX_CHUNK_EIN")) && atol(e) > 0) t.max_chunk_ein = atol(e);
+  t.split = !first_is("NDPP_HIP_NO_SPLIT", '1');
+  if ((e = getenv("NDPP_HIP_SPLIT_BELOW_X"))) t.split_x = atof(e);
+  t.gauss = !first_is("NDPP_HIP_GAUSS", '0');
+  t.gauss_phased = !first_is("NDPP_HIP_GAUSS_PHASED", '0');
+  t.sort = !first_is("NDPP_HIP_NO_SORT", '1');
+  if ((e = getenv("NDPP_HIP_TWO_CONTEXTS_MIN"))) t.two_min = atol(e);
+  if ((e = getenv("NDPP_HIP_TWO_CONTEXTS_MAX"))) t.two_max = atol(e);
+  const FgBatch d{};
+  t.gl_ratio = (e = getenv("NDPP_HIP_GAUSS_RATIO")) ? atof(e) : d.gl_ratio;
+  t.gl_near = (e = getenv("NDPP_HIP_GAUSS_NEAR")) ? atoi(e) != 0 : d.gl_near;
+  t.gl_amin = (e = getenv("NDPP_HIP_GAUSS_AMIN")) ? atof(e) : d.gl_amin;
+  t.gl_cert_depth = (e = getenv("NDPP_HIP_GAUSS_DEPTH")) ? std::min(std::max(atoi(e), 0), 10) : d.gl_cert_depth;
+  t.gl_cert_depth_near =
+      (e = getenv("NDPP_HIP_GAUSS_DEPTH_NEAR")) ? std::min(std::max(atoi(e), 0), 10) : d.gl_cert_depth_near;
+  t.gl_graded = (e = getenv("NDPP_HIP_GAUSS_GRADED")) ? std::min(std::max(atoi(e), 0), 20) : d.gl_graded;
+  t.gl_panels = (e = getenv("NDPP_HIP_GAUSS_PANELS")) ? std::min(std::max(atoi(e), 8), 1024) : d.gl_panels;
+  return t;
+}
+
 // How one batch is laid out in the cached workspace and how many outer-tree nodes fit.
 struct BatchPlan {
   int joint, nch;             // joint = 1: one job per E_in walks both rows as one union tree
-  int mu_blocks, split_below;
+  int num_cu, mu_blocks, split_below;
+  int nb_sort;                // buckets of the level sort: weight classes x masks of L orders (fg_node_bucket)
   size_t mu_threads, seg_doubles, gstack_doubles, ctx_fixed, fixed, need;
   size_t nodes_per_ein;       // arena guess per incoming energy
   long ncap;                  // nodes in the arena
   long max_jobs;              // jobs (and calls) of the largest chunk
   long spare_ein;             // arena room beyond the guess, in incoming energies per context
   int contexts;               // pipeline contexts the batch may run side by side (workspace is carved for that many)
-  long cap_ein;               // test hook: at most this many incoming energies per chunk (0 = no cap)
-  double strict_x, strict_cold, rough_rho;
 };
 
-int plan_batch(const ndpp_params* p, int n_ein, int n_rows, int G, int rows_per_ein, Workspace& g_ws, BatchPlan& pl) {
+int plan_batch(const ndpp_params* p, int n_ein, int n_rows, int G, int rows_per_ein, const FgTunables& t,
+               Workspace& g_ws, BatchPlan& pl) {
   const int L = p->order, GL = G * L;
   size_t free_b = 0, total_b = 0;
-  arithmetic_switch(G, pl.strict_x, pl.strict_cold, pl.rough_rho);
-  const char* nj = getenv("NDPP_HIP_NO_JOINT");
-  pl.joint = (rows_per_ein == 2 && L <= kJointMaxL && !(nj && nj[0] == '1')) ? 1 : 0;
+  pl.joint = (rows_per_ein == 2 && L <= kJointMaxL && t.joint) ? 1 : 0;
   pl.nch = (pl.joint ? 2 : 1) * L;
+  pl.nb_sort = kSortClasses << L;
   const size_t per_call_tree = (size_t)G * kSegPerGroup;
-  // test hooks: NDPP_HIP_NODES_PER_CALL overrides the arena guess (a small value forces the
-  // overflow -> halve-the-chunk path), NDPP_HIP_MAX_CHUNK_EIN caps the chunk (forces chunking)
-  const char* e_nodes = getenv("NDPP_HIP_NODES_PER_CALL");
-  const char* e_chunk = getenv("NDPP_HIP_MAX_CHUNK_EIN");
-  const size_t guess = (e_nodes && atol(e_nodes) > 0) ? (size_t)atol(e_nodes) : (size_t)kNodesPerCallGuess;
+  const size_t guess = t.nodes_per_call > 0 ? (size_t)t.nodes_per_call : (size_t)kNodesPerCallGuess;
   // per call at least 3 nodes per root: the task arrays hold 2 * ncap records and level 0
   // needs 5 per root.  The union tree of two similar rows is barely larger than either.
   pl.contexts = 2;
-  pl.spare_ein = (e_nodes && atol(e_nodes) > 0) ? 0 : kArenaSpareEin;   // (the hook means the guess to bind)
+  pl.spare_ein = t.nodes_per_call > 0 ? 0 : kArenaSpareEin;   // (the hook means the guess to bind)
   const size_t per_call = std::max<size_t>(guess, 3 * per_call_tree);
   pl.nodes_per_ein = pl.joint ? std::max<size_t>((guess * 5) / 4, 3 * per_call_tree) : per_call * rows_per_ein;
   if (g_ws.num_cu == 0) {
@@ -568,6 +615,7 @@ int plan_batch(const ndpp_params* p, int n_ein, int n_rows, int G, int rows_per_
     HIP_TRY(hipGetDeviceProperties(&prop, dev));
     g_ws.num_cu = prop.multiProcessorCount;
   }
+  pl.num_cu = g_ws.num_cu;
   pl.mu_blocks = g_ws.num_cu * kMuBlocksPerCU;      // the most any walk launches
   pl.mu_threads = (size_t)pl.mu_blocks * kWave;
   // (the global part of the sibling stacks is addressed with 24-bit multiplies: fg_device.h DevMuStack)
@@ -586,11 +634,8 @@ int plan_batch(const ndpp_params* p, int n_ein, int n_rows, int G, int rows_per_
   // 1160 / 1156 ms, 100 000: 2354 / 2345 / 2141.  The segment slots are sized for what the batch
   // can need (a small call does not reserve gigabytes): at most 128 inner integrals per incoming energy
   // and level are provided for; a level with more is walked unsplit, which gives the same bits.
-  const char* ns = getenv("NDPP_HIP_NO_SPLIT");
-  double split_x = 32.0;
-  if (const char* e = getenv("NDPP_HIP_SPLIT_BELOW_X")) split_x = atof(e);   // measurement hook
   const size_t split_cap = std::min<size_t>((size_t)1 << 22, std::max<size_t>((size_t)n_ein * 128, (size_t)1 << 16));
-  pl.split_below = (ns && ns[0] == '1') ? 0 : (int)std::min<size_t>((size_t)(split_x * pl.mu_threads), split_cap);
+  pl.split_below = t.split ? (int)std::min<size_t>((size_t)(t.split_x * pl.mu_threads), split_cap) : 0;
   pl.seg_doubles = (size_t)pl.split_below * kSplit * pl.nch;
   // per pipeline context (there are two, see run_batch_d): split-walk segments, global stack part,
   // sort histogram, level counters
@@ -620,14 +665,452 @@ int plan_batch(const ndpp_params* p, int n_ein, int n_rows, int G, int rows_per_
   // that a small batch of heavy trees is not held to it)
   ncap = std::min<size_t>(ncap, ((size_t)n_ein + pl.contexts * pl.spare_ein) * pl.nodes_per_ein);
   ncap = std::min<size_t>(ncap, (size_t)0x7fffffff / 5);
-  pl.cap_ein = (e_chunk && atol(e_chunk) > 0) ? atol(e_chunk) : 0;
-  if (pl.cap_ein) ncap = std::min<size_t>(ncap, (size_t)pl.cap_ein * pl.nodes_per_ein);
+  if (t.max_chunk_ein) ncap = std::min<size_t>(ncap, (size_t)t.max_chunk_ein * pl.nodes_per_ein);
   if (ncap < pl.nodes_per_ein)
     return fail(NDPP_ENOMEM, "not enough device memory for one incoming energy (free %zu)", free_b);
   pl.ncap = (long)ncap;
   pl.max_jobs = (long)std::min<size_t>((size_t)n_ein, ncap / pl.nodes_per_ein) * rows_per_ein;
   pl.need = pl.fixed + (size_t)pl.ncap * node_bytes + (size_t)pl.max_jobs * per_job_bytes;
   return NDPP_OK;
+}
+
+// The one owner of a hipEvent_t in this file: created at its first record, destroyed with its owner.
+struct Event {
+  hipEvent_t e = nullptr;
+  Event() = default;
+  Event(Event&& o) noexcept : e(o.e) { o.e = nullptr; }
+  ~Event() { if (e) (void)hipEventDestroy(e); }
+  hipError_t record(hipStream_t s) {
+    const hipError_t rc = e ? hipSuccess : hipEventCreate(&e);
+    return rc == hipSuccess ? hipEventRecord(e, s) : rc;
+  }
+};
+struct EventPair { Event before, after; };     // around one kernel
+
+// One batch call as run_batch_d received it (every array on the device): what the steps below share.
+struct BatchCall {
+  const ndpp_params* p;
+  double A, kT, cutoff;
+  int n_ein, n_rows, G, rows_per_ein;
+  const double *ein, *w_hi, *f_tab, *e_bins;
+  const int* row_lo;
+  double* out;
+  hipStream_t stream;
+  NucArrays nuc;              // mixed-nuclide batch; else every pointer null
+  int GL() const { return G * p->order; }
+};
+
+// what every pipeline context owns besides its share of the node arena
+struct Slot {
+  int *lvl_cnt, *next_task, *overflow, *mask_hist, *mu_nodes;
+  double *seg, *gstack;
+  hipStream_t s;
+};
+
+// The head of the workspace: what the whole call shares and one Slot per context; the node arena follows.
+struct BatchHead {
+  int *fg_list, *f4_list, *fgs_list;   // incoming energies by class: free gas, file4, free gas in the strict stages
+  int* rough;                          // per table row: not linear in mu (fg_rough_kernel)
+  int* counters;                       // list lengths and bad-input flags (classify_batch)
+  unsigned long long* dstats;
+  int* mask_rank;                      // [2^L] sort keys: the orders active in any row
+  Slot slot[kNumFgContexts];
+  int n_fast = 0, n_f4 = 0, n_strict = 0;   // lengths of the three lists (classify_batch)
+  BatchHead(Carver& cv, const BatchCall& a, const BatchPlan& pl) {
+    fg_list = cv.take<int>(a.n_ein);
+    f4_list = cv.take<int>(a.n_ein);
+    fgs_list = cv.take<int>(a.n_ein);
+    rough = cv.take<int>(a.n_rows);
+    counters = cv.take<int>(64);
+    dstats = cv.take<unsigned long long>(kNumStats);
+    mask_rank = cv.take<int>((size_t)1 << a.p->order);
+    for (int k = 0; k < pl.contexts; ++k) {
+      Slot& sl = slot[k];
+      sl.lvl_cnt = cv.take<int>(kMaxLevels + 2);
+      sl.next_task = cv.take<int>(2 * (kMaxLevels + 2));     // per level: the walk's, the Gauss stage's
+      sl.overflow = cv.take<int>(64);
+      sl.mu_nodes = cv.take<int>(64);
+      sl.mask_hist = cv.take<int>(pl.nb_sort);
+      sl.seg = cv.take<double>(pl.seg_doubles + 1);
+      sl.gstack = cv.take<double>(pl.gstack_doubles + 1);
+      sl.s = a.stream;
+    }
+  }
+};
+
+// bucket of a mask: more active orders first (the longer integrals start first), then by value
+hipError_t upload_mask_rank(int* dst, int nb, hipStream_t stream) {
+  std::vector<int> idx(nb), rank(nb);
+  for (int m = 0; m < nb; ++m) idx[m] = m;
+  std::stable_sort(idx.begin(), idx.end(), [](int x, int y) {
+    return __builtin_popcount((unsigned)x) > __builtin_popcount((unsigned)y);
+  });
+  for (int k = 0; k < nb; ++k) rank[idx[k]] = k;
+  hipError_t e = hipMemcpyAsync(dst, rank.data(), sizeof(int) * nb, hipMemcpyHostToDevice, stream);
+  if (e != hipSuccess) return e;
+  return hipStreamSynchronize(stream);   // rank[] is a local
+}
+
+// Checks row_lo and nuc_of_ein, flags the table rows that are not linear in mu and sorts the incoming
+// energies into the three lists of the head.  Waits for the device: the list lengths decide what follows.
+int classify_batch(const BatchCall& a, const FgTunables& t, bool look_at_tables, BatchHead& h) {
+  hipStream_t stream = a.stream;
+  HIP_TRY(hipMemsetAsync(h.counters, 0, 64 * sizeof(int), stream));
+  HIP_TRY(hipMemsetAsync(h.dstats, 0, kNumStats * sizeof(unsigned long long), stream));
+  const dim3 grid(gs_blocks(a.n_ein)), block(256);
+  hipLaunchKernelGGL(check_rows_kernel, grid, block, 0, stream, a.n_ein, a.row_lo, a.n_rows, a.rows_per_ein,
+                     h.counters + 3);
+  if (a.nuc.nuc_of_ein)
+    hipLaunchKernelGGL(check_nuc_kernel, grid, block, 0, stream, a.n_ein, a.nuc.nuc_of_ein, a.nuc.n_nuc,
+                       h.counters + 4);
+  if (look_at_tables)
+    hipLaunchKernelGGL(fg_rough_kernel, dim3(std::min(a.n_rows, 4096)), block, 0, stream, a.n_rows, a.p->mu_bins,
+                       a.f_tab, t.rough_rho, h.rough);
+  hipLaunchKernelGGL(classify_kernel, grid, block, 0, stream, a.n_ein, a.ein, a.cutoff, h.fg_list, h.counters + 0,
+                     h.f4_list, h.counters + 1, a.nuc.nuc_of_ein, a.nuc.cutoff, a.out, a.GL(),
+                     t.strict_x, t.strict_cold, a.A, a.kT, a.nuc.A, a.nuc.kT, h.fgs_list, h.counters + 5,
+                     look_at_tables ? h.rough : nullptr, a.row_lo, a.rows_per_ein, a.n_rows);
+  int hc[6];
+  HIP_TRY(hipMemcpyAsync(hc, h.counters, sizeof(hc), hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  if (hc[3]) return fail(NDPP_EINVAL, "row_lo outside [0, n_rows-%d]", a.rows_per_ein);
+  if (hc[4]) return fail(NDPP_EINVAL, "nuc_of_ein outside [0, n_nuc)");
+  h.n_fast = hc[0], h.n_f4 = hc[1], h.n_strict = hc[5];
+  return NDPP_OK;
+}
+
+// The stage table (kernels.h FgStages) of this translation unit's arithmetic: the product's, or in a strict
+// library the strict one again.  (Internal linkage keeps these lambdas out of the device code; the exported
+// strict table needs plain functions for that: fg_strict_stages.hip.)
+inline const FgBatch& own(const void* batch) { return *static_cast<const FgBatch*>(batch); }
+const FgStages kFgOwnStages = {   // setup, prep, seg_zero, mu, combine, node, reduce, assemble
+    [](const void* b, size_t, hipStream_t s) { launch_fg_setup(own(b), s); return 0; },
+    [](const void* b, size_t, int level, hipStream_t s) { launch_fg_prep(own(b), level, s); return 0; },
+    [](const void* b, size_t, int level, hipStream_t s) { launch_fg_seg_zero(own(b), level, s); return 0; },
+    [](const void* b, size_t, int level, int num_cu, double* gstack, int* counter, hipStream_t s) {
+      launch_mu_any(own(b), level, num_cu, gstack, counter, s); return 0; },
+    [](const void* b, size_t, int level, hipStream_t s) { launch_fg_combine(own(b), level, s); return 0; },
+    [](const void* b, size_t, int level, hipStream_t s) { launch_fg_node(own(b), level, s); return 0; },
+    [](const void* b, size_t, int level, hipStream_t s) { launch_fg_reduce(own(b), level, s); return 0; },
+    [](const void* b, size_t, hipStream_t s) { launch_fg_assemble(own(b), s); return 0; },
+};
+
+// ---- free-gas part: pipeline contexts -------------------------------------
+// One context = one list of incoming energies in one arithmetic, walked chunk by chunk through
+// its own share of the node arena on its own stream.  The product and the strict list are two
+// contexts; a lone list of at least kTwoContextsMinEin energies is dealt round-robin to two
+// (bit-identical results: an incoming energy's moments do not depend on what shares its
+// chunk).  The inner walk of one context then fills what the other leaves idle -- the tail of
+// a level, during which a few lanes finish their integrals, and the sort / limits / node
+// kernels between two levels.
+struct FgCtx {
+  FgBatch B;
+  Slot sl;
+  bool strict;
+  const FgStages* stages;     // the stages of this context's arithmetic
+  const int* list;            // this context's k-th energy is list[k * lstride]
+  int lstride;
+  long n, done, chunk_ein, this_ein;
+  double *job_ein, *job_A, *job_kT;
+  int *job_row, *order;
+  bool inflight;
+  std::vector<EventPair> walk_ev;    // around each fg_mu_kernel of the chunk in flight
+  std::vector<EventPair> gauss_ev;   // ... each Gauss kernel
+};
+
+// deals the two free-gas lists to contexts and decides whether these run side by side
+std::vector<FgCtx> deal_contexts(const BatchHead& h, const FgTunables& t, const BatchPlan& pl, bool& side_by_side) {
+  std::vector<FgCtx> ctx;
+  auto add = [&](const int* list, int parts, long len, bool strict) {
+    for (int j = 0; j < parts; ++j) {       // part j: list[j], list[j + parts], ...
+      FgCtx c{};
+      c.list = list + j; c.lstride = parts; c.n = (len - j + parts - 1) / parts; c.strict = strict;
+      c.stages = strict ? &fg_strict_stages() : &kFgOwnStages;
+      if (c.n > 0) ctx.push_back(std::move(c));
+    }
+  };
+  // Two contexts in all: the product and the strict list, or a lone list of two_min ... two_max - 1
+  // incoming energies dealt to two (kTwoContextsMaxEin).  (Measured with 3 and 4:
+  // 12 500 / 25 000 / 100 000 H-1 energies run at 53.3 / 60.4 / 68.7 k E_in*orders/s with two,
+  // 52.5 / 57.4 / 67.4 with three, 53.7 / 57.0 / 67.1 with four.)
+  auto parts_of = [&](long len, int room) {
+    if (len <= 0) return 0;
+    const int k = (t.two_min > 0 && len >= t.two_min && len < t.two_max && len >= room) ? room : 1;
+    return std::max(1, k);
+  };
+  const int k_strict = parts_of(h.n_strict, h.n_fast > 0 ? std::max(1, pl.contexts / 2) : pl.contexts);
+  const int k_fast = parts_of(h.n_fast, std::max(1, pl.contexts - k_strict));
+  add(h.fg_list, k_fast, h.n_fast, false);
+  add(h.fgs_list, k_strict, h.n_strict, true);
+  // the contexts run side by side when every one of them gets room for at least one incoming
+  // energy, else one after the other through the whole arena
+  const int nctx = (int)ctx.size();
+  side_by_side = nctx > 1 && nctx <= pl.contexts && t.two_min > 0 && (size_t)pl.ncap >= (size_t)nctx * pl.nodes_per_ein;
+  return ctx;
+}
+
+// gives every context its stream, its slot and its share of the node arena, carved into its FgBatch
+int carve_contexts(std::vector<FgCtx>& ctx, bool side_by_side, const BatchCall& a, const FgTunables& t,
+                   const BatchPlan& pl, const BatchHead& h, Carver cv, bool gauss_on, Workspace& ws) {
+  const int nctx = (int)ctx.size(), ncap = (int)pl.ncap, L = a.p->order;
+  for (int k = 1; side_by_side && k < nctx; ++k)
+    if (!ws.aux[k - 1]) HIP_TRY(hipStreamCreateWithFlags(&ws.aux[k - 1], hipStreamNonBlocking));
+  FgBatch T;
+  T.gl_ratio = t.gl_ratio; T.gl_near = t.gl_near; T.gl_amin = t.gl_amin; T.gl_cert_depth = t.gl_cert_depth;
+  T.gl_cert_depth_near = t.gl_cert_depth_near; T.gl_graded = t.gl_graded; T.gl_panels = t.gl_panels;
+  T.G = a.G; T.L = L; T.M = a.p->mu_bins; T.A = a.A; T.kT = a.kT; T.f_tab = a.f_tab; T.e_bins = a.e_bins;
+  T.sab_threshold = a.p->sab_threshold; T.brent_thresh = a.p->brent_mu_thresh;
+  T.mu_tol = a.p->adaptive_mu_tol; T.eout_tol = a.p->adaptive_eout_tol;
+  T.mu_its = a.p->adaptive_mu_its; T.eout_its = a.p->adaptive_eout_its;
+  T.grid = make_mu_grid(T.M);
+  T.R = pl.joint ? a.rows_per_ein : 1;
+  T.mask_rank = h.mask_rank; T.split_below = pl.split_below; T.stats = h.dstats;
+  long n_all = 0;
+  for (auto& c : ctx) n_all += c.n;
+  char* const arena = cv.p;
+  long cap_left = ncap;
+  for (int k = 0; k < nctx; ++k) {
+    FgCtx& c = ctx[k];
+    if (!side_by_side) cv.p = arena;             // every context in turn takes the whole arena
+    c.sl = h.slot[side_by_side ? k : 0];
+    if (side_by_side && k > 0) c.sl.s = ws.aux[k - 1];
+    long share = side_by_side ? std::max<long>((long)pl.nodes_per_ein,
+                                               (long)((double)ncap * (c.n + pl.spare_ein) /
+                                                      (n_all + (long)nctx * pl.spare_ein))) : ncap;
+    share = std::min<long>(share, (long)((size_t)(c.n + pl.spare_ein) * pl.nodes_per_ein));
+    if (side_by_side) {
+      share = std::min(share, cap_left - (long)(nctx - 1 - k) * (long)pl.nodes_per_ein);
+      cap_left -= share;
+    }
+    const long max_jobs = std::min<long>(c.n, share / (long)pl.nodes_per_ein) * a.rows_per_ein;
+    FgBatch& B = c.B;
+    B = T;
+    B.ncap = (int)share;
+    B.node_a = cv.take<double>(B.ncap); B.node_b = cv.take<double>(B.ncap);
+    B.node_F = cv.take<double>((size_t)5 * pl.nch * B.ncap);
+    B.node_S = cv.take<double>((size_t)pl.nch * B.ncap);
+    B.node_info = cv.take<int>((size_t)4 * B.ncap);
+    B.tcap = 2 * B.ncap;
+    B.t_mulo = cv.take<double>(B.tcap); B.t_muhi = cv.take<double>(B.tcap);
+    B.t_X = cv.take<double>((size_t)3 * (pl.joint ? 2 : 1) * B.tcap);
+    // the Gauss rule for the inner integrals the reference has converged: product-arithmetic
+    // contexts only, and only when the batch's tables were looked at (a context of the product
+    // arithmetic then holds energies of rows linear in mu only)
+    B.t_gl = (gauss_on && !c.strict) ? cv.take<unsigned char>(B.tcap) : nullptr;
+    B.job_ein = c.job_ein = cv.take<double>(max_jobs);
+    B.job_row = c.job_row = cv.take<int>(max_jobs);
+    c.job_A = cv.take<double>(max_jobs); c.job_kT = cv.take<double>(max_jobs);
+    if (a.nuc.nuc_of_ein) { B.job_A = c.job_A; B.job_kT = c.job_kT; }
+    B.raw = cv.take<double>((size_t)max_jobs * a.GL());
+    c.order = cv.take<int>(B.ncap);
+    B.order = t.sort ? c.order : nullptr;
+    B.seg = pl.split_below ? c.sl.seg : nullptr;
+    B.lvl_cnt = c.sl.lvl_cnt; B.next_task = c.sl.next_task; B.overflow = c.sl.overflow;
+    if (cv.p > cv.end)
+      return fail(NDPP_ENOMEM, "workspace carve overran (%zu > %zu)",
+                  (size_t)(cv.p - ws.base), ws.bytes);
+    c.chunk_ein = std::max<long>(1, max_jobs / a.rows_per_ein);
+    if (t.max_chunk_ein) c.chunk_ein = std::min<long>(c.chunk_ein, t.max_chunk_ein);
+  }
+  return NDPP_OK;
+}
+
+// whatever path leaves run_batch_d, nothing may still be running in the arena
+struct Drain {
+  hipStream_t first;
+  hipStream_t* more;
+  int n_more;
+  ~Drain() {
+    (void)hipStreamSynchronize(first);
+    for (int k = 0; k < n_more; ++k) (void)hipStreamSynchronize(more[k]);
+  }
+};
+
+// The events of a batch call and its three timing outputs: ndpp_stats, ndpp_last_gpu_ms(), the profile families.
+struct FgTiming {
+  Event ev0, ev1;             // around the whole call
+  Event ev_f4;                // after classification + the file4 kernel; the rest is the free-gas pipeline
+  std::vector<std::pair<float, float>> spans;   // (start, end) of each walk and Gauss kernel
+  double mu_sum_ms = 0.0, gauss_sum_ms = 0.0;
+  double level_ms[32] = {0};
+  int mu_launches = 0;
+
+  // a retired chunk's pairs, one per level: the walk's, or the Gauss stage's (counted in mu_busy_ms as well)
+  void fold(std::vector<EventPair>& pairs, bool walk) {
+    int level = 0;
+    for (auto& e : pairs) {
+      float t0 = 0.f, t1 = 0.f;
+      if (hipEventElapsedTime(&t0, ev0.e, e.before.e) == hipSuccess &&
+          hipEventElapsedTime(&t1, ev0.e, e.after.e) == hipSuccess) {
+        (walk ? mu_sum_ms : gauss_sum_ms) += t1 - t0;
+        if (walk && level < 32) level_ms[level] += t1 - t0;
+        spans.emplace_back(t0, t1);
+      }
+      ++level;
+      if (walk) ++mu_launches;
+    }
+    pairs.clear();
+  }
+
+  // after the final synchronise.  hs: the device's counters; contexts: how many ran side by side
+  void publish(const unsigned long long* hs, int contexts, ndpp_stats* stats) {
+    // time during which at least one walk or Gauss kernel was in flight
+    double mu_ms = 0.0;
+    std::sort(spans.begin(), spans.end());
+    float end = -1.f;
+    for (auto& sp : spans) {
+      if (sp.second <= end) continue;
+      mu_ms += sp.second - std::max(sp.first, end);
+      end = sp.second;
+    }
+    float ms = 0.f, ms4 = 0.f;
+    if (hipEventElapsedTime(&ms, ev0.e, ev1.e) == hipSuccess) ndpp::g_last_gpu_ms = ms;
+    if (hipEventElapsedTime(&ms4, ev0.e, ev_f4.e) == hipSuccess) {
+      profile_add(kProfFile4, ms4);
+      profile_add(kProfFreegasMu, mu_ms);
+      profile_add(kProfFreegasOther, std::max(0.0, (double)ms - ms4 - mu_ms));
+    }
+    if (!stats) return;
+    stats->k_evals = hs[kStatKEvals];
+    stats->mu_visits = hs[kStatMuVisits];
+    stats->mu_integrals = hs[kStatMuIntegrals];
+    stats->eout_nodes = hs[kStatEoutNodes];
+    stats->wave_iters = hs[kStatWaveIters];
+    stats->lane_iters = hs[kStatLaneIters];
+    stats->order_visits = hs[kStatOrderVisits];
+    stats->gauss_integrals = hs[kStatGaussIntegrals];
+    stats->gauss_ms = gauss_sum_ms;
+    for (int k = 0; k < 32; ++k) stats->mu_level_ms[k] = level_ms[k];
+    stats->mu_kernel_ms = mu_sum_ms;
+    stats->mu_busy_ms = mu_ms;
+    stats->mu_kernel_launches = mu_launches;
+    stats->contexts = contexts;
+    stats->total_ms = ms;
+  }
+};
+
+// queue one chunk of a context on its stream (nothing here waits for the device)
+int enqueue_chunk(FgCtx& c, const BatchCall& a, const FgTunables& t, const BatchPlan& pl) {
+  FgBatch& B = c.B;
+  hipStream_t s = c.sl.s;
+  const FgStages& st = *c.stages;
+  const int rows_per_ein = a.rows_per_ein, GL = a.GL();
+  for (;;) {
+    c.this_ein = std::min<long>(c.chunk_ein, c.n - c.done);
+    B.n_jobs = pl.joint ? (int)c.this_ein : (int)(c.this_ein * rows_per_ein);
+    const int ntrees = B.n_trees();
+    if ((long)ntrees * kSegPerGroup <= (long)B.tcap && ntrees <= B.ncap) break;
+    // more roots than the arena can even start with: take fewer energies
+    if (c.chunk_ein <= 1) return fail(NDPP_EOVERFLOW, "arena of %d nodes is too small for one E_in", B.ncap);
+    c.chunk_ein = std::max<long>(1, c.chunk_ein / 2);
+  }
+  const int* lst = c.list + (size_t)c.done * c.lstride;
+  HIP_TRY(hipMemsetAsync(c.sl.lvl_cnt, 0, (kMaxLevels + 2) * sizeof(int), s));
+  HIP_TRY(hipMemsetAsync(c.sl.next_task, 0, 2 * (kMaxLevels + 2) * sizeof(int), s));
+  HIP_TRY(hipMemsetAsync(c.sl.overflow, 0, sizeof(int), s));
+  hipLaunchKernelGGL(fg_set_int_kernel, dim3(1), dim3(1), 0, s, c.sl.lvl_cnt, B.n_trees());
+  hipLaunchKernelGGL(make_jobs_kernel, dim3(gs_blocks(B.n_jobs)), dim3(256), 0, s, B.n_jobs, rows_per_ein, pl.joint,
+                     lst, c.lstride, a.ein, a.row_lo, c.job_ein, c.job_row, a.nuc.nuc_of_ein, a.nuc.A, a.nuc.kT,
+                     c.job_A, c.job_kT);
+  if (int rc = st.setup(&B, sizeof B, s)) return rc;
+  const int nlev = B.eout_its + 1;
+  for (int level = 0; level < nlev; ++level) {
+    // the mu limits come out of Brent iterations that stop at a tolerance: in the product
+    // arithmetic they would end ~1e-7 away from the reference's, and every inner integral
+    // with them.  So the prep stage of every batch runs in the reference arithmetic
+    // (fg_strict_stages.hip; 0.2 % of a pass).
+    B.mu_nodes = nullptr;
+    if (int rc = fg_strict_stages().prep(&B, sizeof B, level, s)) return rc;
+    if (B.t_gl) {
+      c.gauss_ev.emplace_back();
+      HIP_TRY(c.gauss_ev.back().before.record(s));
+      launch_gauss_any(B, level, pl.num_cu, t.gauss_phased, s);
+      HIP_TRY(c.gauss_ev.back().after.record(s));
+    }
+    if (t.sort) {
+      // nodes sorted by weight class and the orders still active in any row; nodes with nothing
+      // left for the walk last (fg_node_bucket)
+      B.mu_nodes = c.sl.mu_nodes;
+      HIP_TRY(hipMemsetAsync(c.sl.mask_hist, 0, sizeof(int) * pl.nb_sort, s));
+      hipLaunchKernelGGL(fg_sort_count_kernel, dim3(1024), dim3(256), 0, s, B, level, pl.nb_sort, c.sl.mask_hist);
+      hipLaunchKernelGGL(fg_sort_scan_kernel, dim3(1), dim3(256), 0, s, c.sl.mask_hist, pl.nb_sort, c.sl.mu_nodes);
+      hipLaunchKernelGGL(fg_sort_scatter_kernel, dim3(1024), dim3(256), 0, s, B, level, pl.nb_sort,
+                         c.sl.mask_hist, c.order);
+    }
+    if (B.seg)
+      if (int rc = st.seg_zero(&B, sizeof B, level, s)) return rc;
+    c.walk_ev.emplace_back();
+    HIP_TRY(c.walk_ev.back().before.record(s));
+    if (int rc = st.mu(&B, sizeof B, level, pl.num_cu, c.sl.gstack, c.sl.next_task + level, s)) return rc;
+    HIP_TRY(c.walk_ev.back().after.record(s));
+    if (int rc = st.combine(&B, sizeof B, level, s)) return rc;
+    B.mu_nodes = nullptr;
+    if (int rc = st.node(&B, sizeof B, level, s)) return rc;
+  }
+  for (int level = nlev - 1; level >= 0; --level)
+    if (int rc = st.reduce(&B, sizeof B, level, s)) return rc;
+  if (int rc = st.assemble(&B, sizeof B, s)) return rc;
+  if (rows_per_ein == 2)
+    hipLaunchKernelGGL(blend_kernel, dim3(gs_blocks(c.this_ein * GL)), dim3(256), 0, s,
+                       (int)c.this_ein, lst, c.lstride, B.raw, a.w_hi, GL, a.out);
+  else
+    hipLaunchKernelGGL(copy_raw_kernel, dim3(gs_blocks(c.this_ein * GL)), dim3(256), 0, s,
+                       (int)c.this_ein, lst, c.lstride, B.raw, GL, a.out);
+  c.inflight = true;
+  return NDPP_OK;
+}
+
+// the chunk of a context has left the device: its timings, and whether it has to be redone
+int retire_chunk(FgCtx& c, FgTiming& tm) {
+  c.inflight = false;
+  int ovf = 0;
+  HIP_TRY(hipMemcpyAsync(&ovf, c.sl.overflow, sizeof(int), hipMemcpyDeviceToHost, c.sl.s));
+  HIP_TRY(hipStreamSynchronize(c.sl.s));
+  HIP_TRY(hipGetLastError());
+  tm.fold(c.walk_ev, true);
+  tm.fold(c.gauss_ev, false);
+  if (ovf) {
+    // the adaptive trees outgrew the arena: redo this chunk with half the energies
+    if (c.chunk_ein <= 1)
+      return fail(NDPP_EOVERFLOW, "outer tree of one E_in exceeds %d nodes", c.B.ncap);
+    c.chunk_ein = std::max<long>(1, c.chunk_ein / 2);
+  } else {
+    c.done += c.this_ein;
+  }
+  return NDPP_OK;
+}
+
+// The two driving loops.  One context after the other, chunk by chunk; or side by side: every context keeps
+// one chunk in flight on its own stream, and whichever finishes is retired and refilled.
+int run_contexts(std::vector<FgCtx>& ctx, bool side_by_side, const BatchCall& a, const FgTunables& t,
+                 const BatchPlan& pl, FgTiming& tm) {
+  if (!side_by_side) {
+    for (auto& c : ctx)
+      while (c.done < c.n) {
+        if (int rc = enqueue_chunk(c, a, t, pl)) return rc;
+        if (int rc = retire_chunk(c, tm)) return rc;
+      }
+    return NDPP_OK;
+  }
+  for (auto& c : ctx)
+    if (int rc = enqueue_chunk(c, a, t, pl)) return rc;
+  for (;;) {
+    int live = 0;
+    bool moved = false;
+    for (auto& c : ctx) {
+      if (!c.inflight) continue;
+      ++live;
+      const hipError_t q = hipStreamQuery(c.sl.s);
+      if (q == hipErrorNotReady) continue;
+      if (q != hipSuccess) return fail(NDPP_EDEVICE, "free-gas pipeline failed: %s", hipGetErrorString(q));
+      if (int rc = retire_chunk(c, tm)) return rc;
+      if (c.done < c.n)
+        if (int rc = enqueue_chunk(c, a, t, pl)) return rc;
+      moved = true;
+    }
+    if (!live) return NDPP_OK;
+    if (!moved) std::this_thread::sleep_for(std::chrono::microseconds(50));
+  }
 }
 
 // The device-resident batch (everything *_d).  rows_per_ein = 2 for the
@@ -650,492 +1133,50 @@ int run_batch_d(const ndpp_params* p, double A, double kT, double cutoff, double
   if (!ein_d || !row_lo_d || !f_tab_d || !e_bins_d || !out_d ||
       (rows_per_ein == 2 && !w_hi_d))
     return fail(NDPP_EINVAL, "NULL array argument");
-
+  const BatchCall a{p, A, kT, cutoff, n_ein, n_rows, G, rows_per_ein, ein_d, w_hi_d, f_tab_d, e_bins_d, row_lo_d,
+                    out_d, stream, na ? *na : NucArrays{}};
+  const FgTunables t = read_fg_tunables(G);
   Workspace* wsp = nullptr;
   rc = current_workspace(&wsp);
   if (rc) return rc;
   Workspace& g_ws = *wsp;
   std::lock_guard<std::mutex> lock(g_ws.mu);
-  const int L = p->order, M = p->mu_bins;
-  const int GL = G * L;
-
   BatchPlan pl;
-  rc = plan_batch(p, n_ein, n_rows, G, rows_per_ein, g_ws, pl);
+  rc = plan_batch(p, n_ein, n_rows, G, rows_per_ein, t, g_ws, pl);
   if (rc) return rc;
   rc = ensure_workspace(g_ws, pl.need);
   if (rc) return rc;
-  const int joint = pl.joint, split_below = pl.split_below;
-  const int ncap = (int)pl.ncap;
-
-  // (a batch without a free-gas range -- the level reactions' cutoff is 0 -- has nothing to switch)
-  const bool look_at_tables = pl.rough_rho >= 0.0 && (na != nullptr || cutoff > 0.0);
   Carver cv{g_ws.base, g_ws.base + g_ws.bytes};
-  int* fg_list = cv.take<int>(n_ein);
-  int* f4_list = cv.take<int>(n_ein);
-  int* fgs_list = cv.take<int>(n_ein);   // free gas, strict stages
-  int* rough = cv.take<int>(n_rows);     // per table row: not linear in mu (fg_rough_kernel)
-  int* counters = cv.take<int>(64);  // [0]=n_fg [1]=n_f4 [3]=badrow [4]=badnuc [5]=n_fgs
-  unsigned long long* dstats = cv.take<unsigned long long>(kNumStats);
-  const int nb_masks = 1 << L;                         // sort keys: the orders active in any row ...
-  const int nb_sort = kSortClasses * nb_masks;         // ... per weight class (fg_node_bucket)
-  int* mask_rank = cv.take<int>(nb_masks);
-  // what every pipeline context owns besides its share of the node arena
-  struct Slot {
-    int *lvl_cnt, *next_task, *overflow, *mask_hist, *mu_nodes;
-    double *seg, *gstack;
-    hipStream_t s;
-  } slot[kNumFgContexts];
-  for (int k = 0; k < pl.contexts; ++k) {
-    slot[k].lvl_cnt = cv.take<int>(kMaxLevels + 2);
-    slot[k].next_task = cv.take<int>(2 * (kMaxLevels + 2));     // per level: the walk's, the Gauss stage's
-    slot[k].overflow = cv.take<int>(64);
-    slot[k].mu_nodes = cv.take<int>(64);
-    slot[k].mask_hist = cv.take<int>(nb_sort);
-    slot[k].seg = cv.take<double>(pl.seg_doubles + 1);
-    slot[k].gstack = cv.take<double>(pl.gstack_doubles + 1);
-    slot[k].s = stream;
-  }
-  char* const arena = cv.p;
-
-  const char* ng = getenv("NDPP_HIP_GAUSS");        // 0: every inner integral by the adaptive walk
-  const bool gauss_on = NDPP_FAST && look_at_tables && !(ng && ng[0] == '0') &&
+  BatchHead h(cv, a, pl);      // (cv now stands at the node arena)
+  // (a batch without a free-gas range -- the level reactions' cutoff is 0 -- has nothing to switch)
+  const bool look_at_tables = t.rough_rho >= 0.0 && (na != nullptr || cutoff > 0.0);
+  const bool gauss_on = NDPP_FAST && look_at_tables && t.gauss &&
                         fg_gauss_box(p->adaptive_mu_its, p->adaptive_mu_tol);
-  // 0: the Gauss stage one candidate per lane (the previous kernel, kept for comparison); default:
-  // by phases, each run by a wave of candidates that have reached it (fg_gauss_phased_kernel)
-  const char* nph = getenv("NDPP_HIP_GAUSS_PHASED");
-  const bool gauss_phased = !(nph && nph[0] == '0');
-  const char* nsort = getenv("NDPP_HIP_NO_SORT");   // test hook: walk tasks in creation order
-  const bool do_sort = !(nsort && nsort[0] == '1');
-
-  hipEvent_t ev0, ev1;
-  HIP_TRY(hipEventCreate(&ev0));
-  HIP_TRY(hipEventCreate(&ev1));
-  struct EvGuard {
-    hipEvent_t a, b;
-    ~EvGuard() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); }
-  } guard{ev0, ev1};
-
-  {
-    // bucket of a mask: more active orders first (the longer integrals start first), then by value
-    auto upload_rank = [&](int* dst, int nb) -> hipError_t {
-      std::vector<int> idx(nb), rank(nb);
-      for (int m = 0; m < nb; ++m) idx[m] = m;
-      std::stable_sort(idx.begin(), idx.end(), [](int x, int y) {
-        return __builtin_popcount((unsigned)x) > __builtin_popcount((unsigned)y);
-      });
-      for (int k = 0; k < nb; ++k) rank[idx[k]] = k;
-      hipError_t e = hipMemcpyAsync(dst, rank.data(), sizeof(int) * nb, hipMemcpyHostToDevice, stream);
-      if (e != hipSuccess) return e;
-      return hipStreamSynchronize(stream);   // rank[] is a local
-    };
-    HIP_TRY(upload_rank(mask_rank, nb_masks));
-  }
-  HIP_TRY(hipEventRecord(ev0, stream));
-  HIP_TRY(hipMemsetAsync(counters, 0, 64 * sizeof(int), stream));
-  HIP_TRY(hipMemsetAsync(dstats, 0, kNumStats * sizeof(unsigned long long), stream));
-  hipLaunchKernelGGL(check_rows_kernel, dim3(gs_blocks(n_ein)), dim3(256), 0, stream,
-                     n_ein, row_lo_d, n_rows, rows_per_ein, counters + 3);
-  if (na)
-    hipLaunchKernelGGL(check_nuc_kernel, dim3(gs_blocks(n_ein)), dim3(256), 0, stream, n_ein,
-                       na->nuc_of_ein, na->n_nuc, counters + 4);
-  const bool look = look_at_tables;
-  if (look)
-    hipLaunchKernelGGL(fg_rough_kernel, dim3(std::min(n_rows, 4096)), dim3(256), 0, stream, n_rows, M, f_tab_d,
-                       pl.rough_rho, rough);
-  hipLaunchKernelGGL(classify_kernel, dim3(gs_blocks(n_ein)), dim3(256), 0, stream,
-                     n_ein, ein_d, cutoff, fg_list, counters + 0, f4_list, counters + 1,
-                     na ? na->nuc_of_ein : nullptr, na ? na->cutoff : nullptr, out_d, GL,
-                     pl.strict_x, pl.strict_cold, A, kT, na ? na->A : nullptr, na ? na->kT : nullptr, fgs_list,
-                     counters + 5, look ? rough : nullptr, row_lo_d, rows_per_ein, n_rows);
-  int hc[6];
-  HIP_TRY(hipMemcpyAsync(hc, counters, sizeof(hc), hipMemcpyDeviceToHost, stream));
-  HIP_TRY(hipStreamSynchronize(stream));
-  if (hc[3]) return fail(NDPP_EINVAL, "row_lo outside [0, n_rows-%d]", rows_per_ein);
-  if (hc[4]) return fail(NDPP_EINVAL, "nuc_of_ein outside [0, n_nuc)");
-  const int n_fg_fast = hc[0], n_f4 = hc[1], n_fg_strict = hc[5];
-
+  FgTiming tm;
+  HIP_TRY(upload_mask_rank(h.mask_rank, 1 << p->order, stream));
+  HIP_TRY(tm.ev0.record(stream));
+  if ((rc = classify_batch(a, t, look_at_tables, h))) return rc;
   // ---- file4-CM part ------------------------------------------------------
-  hipEvent_t ev_f4;
-  HIP_TRY(hipEventCreate(&ev_f4));
-  struct Ev1 { hipEvent_t e; ~Ev1() { (void)hipEventDestroy(e); } } guard_f4{ev_f4};
-  launch_file4_any(n_f4, f4_list, M, ein_d, row_lo_d, w_hi_d, f_tab_d, A, Q, G,
-                   L, e_bins_d, rows_per_ein, out_d, stream, na ? na->nuc_of_ein : nullptr,
-                   na ? na->A : nullptr, na ? na->Q : nullptr);
-  HIP_TRY(hipEventRecord(ev_f4, stream));
-
-  // ---- free-gas part: pipeline contexts -------------------------------------
-  // One context = one list of incoming energies in one arithmetic, walked chunk by chunk through
-  // its own share of the node arena on its own stream.  The product and the strict list are two
-  // contexts; a lone list of at least kTwoContextsMinEin energies is dealt round-robin to two
-  // (bit-identical results: an incoming energy's moments do not depend on what shares its
-  // chunk).  The inner walk of one context then fills what the other leaves idle -- the tail of
-  // a level, during which a few lanes finish their integrals, and the sort / limits / node
-  // kernels between two levels.
-  struct FgCtx {
-    FgBatch B;
-    Slot sl;
-    bool strict;
-    const int* list;            // this context's k-th energy is list[k * lstride]
-    int lstride;
-    long n, done, chunk_ein, this_ein;
-    int ncap;
-    long max_jobs;
-    double *job_ein, *job_A, *job_kT;
-    int *job_row, *order;
-    bool inflight;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;   // (before, after) each fg_mu_kernel
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> gev;  // ... each fg_gauss_kernel
-  };
-  std::vector<FgCtx> ctx;
-  long two_min = kTwoContextsMinEin, two_max = kTwoContextsMaxEin;
-  if (const char* e = getenv("NDPP_HIP_TWO_CONTEXTS_MIN")) two_min = atol(e);   // test hook; 0 = one at a time
-  if (const char* e = getenv("NDPP_HIP_TWO_CONTEXTS_MAX")) two_max = atol(e);   // test hook
-  {
-    auto add = [&](const int* list, int parts, long n, bool strict) {
-      for (int j = 0; j < parts; ++j) {       // part j: list[j], list[j + parts], ...
-        FgCtx c{};
-        c.list = list + j; c.lstride = parts; c.n = (n - j + parts - 1) / parts; c.strict = strict;
-        if (c.n > 0) ctx.push_back(c);
-      }
-    };
-    // Two contexts in all: the product and the strict list, or a lone list of two_min ... two_max - 1
-    // incoming energies dealt to two (kTwoContextsMaxEin).  (Measured with 3 and 4:
-    // 12 500 / 25 000 / 100 000 H-1 energies run at 53.3 / 60.4 / 68.7 k E_in*orders/s with two,
-    // 52.5 / 57.4 / 67.4 with three, 53.7 / 57.0 / 67.1 with four.)
-    const int total = pl.contexts;
-    auto parts_of = [&](long n, int room) {
-      if (n <= 0) return 0;
-      const int k = (two_min > 0 && n >= two_min && n < two_max && n >= room) ? room : 1;
-      return std::max(1, k);
-    };
-    const int k_strict = parts_of(n_fg_strict, n_fg_fast > 0 ? std::max(1, total / 2) : total);
-    const int k_fast = parts_of(n_fg_fast, std::max(1, total - k_strict));
-    add(fg_list, k_fast, n_fg_fast, false);
-    add(fgs_list, k_strict, n_fg_strict, true);
-  }
+  launch_file4_any(h.n_f4, h.f4_list, p->mu_bins, ein_d, row_lo_d, w_hi_d, f_tab_d, A, Q, G, p->order, e_bins_d,
+                   rows_per_ein, out_d, stream, a.nuc.nuc_of_ein, a.nuc.A, a.nuc.Q);
+  HIP_TRY(tm.ev_f4.record(stream));
+  // ---- free-gas part (FgCtx) ------------------------------------------------
+  bool side_by_side = false;
+  std::vector<FgCtx> ctx = deal_contexts(h, t, pl, side_by_side);
   const int nctx = (int)ctx.size();
-  // the contexts run side by side when every one of them gets room for at least one incoming
-  // energy, else one after the other through the whole arena
-  long n_all = 0;
-  for (auto& c : ctx) n_all += c.n;
-  const bool side_by_side = nctx > 1 && nctx <= pl.contexts && two_min > 0 &&
-                            (size_t)ncap >= (size_t)nctx * pl.nodes_per_ein;
-  for (int k = 1; side_by_side && k < nctx; ++k)
-    if (!g_ws.aux[k - 1]) HIP_TRY(hipStreamCreateWithFlags(&g_ws.aux[k - 1], hipStreamNonBlocking));
-  {
-    FgBatch T;
-    T.G = G; T.L = L; T.M = M; T.A = A; T.kT = kT;
-    T.f_tab = f_tab_d; T.e_bins = e_bins_d;
-    T.sab_threshold = p->sab_threshold; T.brent_thresh = p->brent_mu_thresh;
-    T.mu_tol = p->adaptive_mu_tol; T.eout_tol = p->adaptive_eout_tol;
-    T.mu_its = p->adaptive_mu_its; T.eout_its = p->adaptive_eout_its;
-    T.grid = make_mu_grid(M);
-    T.R = joint ? rows_per_ein : 1;
-    T.mask_rank = mask_rank;
-    T.split_below = split_below;
-    T.stats = dstats;
-    long cap_left = ncap;
-    for (int k = 0; k < nctx; ++k) {
-      FgCtx& c = ctx[k];
-      if (!side_by_side) cv.p = arena;             // every context in turn takes the whole arena
-      c.sl = slot[side_by_side ? k : 0];
-      if (side_by_side && k > 0) c.sl.s = g_ws.aux[k - 1];
-      long share = side_by_side ? std::max<long>((long)pl.nodes_per_ein,
-                                                 (long)((double)ncap * (c.n + pl.spare_ein) /
-                                                        (n_all + (long)nctx * pl.spare_ein))) : ncap;
-      share = std::min<long>(share, (long)((size_t)(c.n + pl.spare_ein) * pl.nodes_per_ein));
-      if (side_by_side) {
-        share = std::min(share, cap_left - (long)(nctx - 1 - k) * (long)pl.nodes_per_ein);
-        cap_left -= share;
-      }
-      c.ncap = (int)share;
-      c.max_jobs = std::min<long>(c.n, share / (long)pl.nodes_per_ein) * rows_per_ein;
-      FgBatch& B = c.B;
-      B = T;
-      B.ncap = c.ncap;
-      B.node_a = cv.take<double>(c.ncap);
-      B.node_b = cv.take<double>(c.ncap);
-      B.node_F = cv.take<double>((size_t)5 * pl.nch * c.ncap);
-      B.node_S = cv.take<double>((size_t)pl.nch * c.ncap);
-      B.node_info = cv.take<int>((size_t)4 * c.ncap);
-      B.tcap = 2 * c.ncap;
-      B.t_mulo = cv.take<double>(B.tcap);
-      B.t_muhi = cv.take<double>(B.tcap);
-      B.t_X = cv.take<double>((size_t)3 * (joint ? 2 : 1) * B.tcap);
-      // the Gauss rule for the inner integrals the reference has converged: product-arithmetic
-      // contexts only, and only when the batch's tables were looked at (a context of the product
-      // arithmetic then holds energies of rows linear in mu only)
-      B.t_gl = (gauss_on && !c.strict) ? cv.take<unsigned char>(B.tcap) : nullptr;
-      // (experiment knobs; the defaults are what profiles/r04/parity_tail_*.log were measured with)
-      if (const char* e = getenv("NDPP_HIP_GAUSS_RATIO")) B.gl_ratio = atof(e);
-      if (const char* e = getenv("NDPP_HIP_GAUSS_NEAR")) B.gl_near = atoi(e) != 0;
-      if (const char* e = getenv("NDPP_HIP_GAUSS_AMIN")) B.gl_amin = atof(e);
-      if (const char* e = getenv("NDPP_HIP_GAUSS_DEPTH")) B.gl_cert_depth = std::min(std::max(atoi(e), 0), 10);
-      if (const char* e = getenv("NDPP_HIP_GAUSS_DEPTH_NEAR")) B.gl_cert_depth_near = std::min(std::max(atoi(e), 0), 10);
-      if (const char* e = getenv("NDPP_HIP_GAUSS_GRADED")) B.gl_graded = std::min(std::max(atoi(e), 0), 20);
-      if (const char* e = getenv("NDPP_HIP_GAUSS_PANELS")) B.gl_panels = std::min(std::max(atoi(e), 8), 1024);
-      c.job_ein = cv.take<double>(c.max_jobs);
-      c.job_row = cv.take<int>(c.max_jobs);
-      B.job_ein = c.job_ein;
-      B.job_row = c.job_row;
-      c.job_A = cv.take<double>(c.max_jobs);
-      c.job_kT = cv.take<double>(c.max_jobs);
-      if (na) { B.job_A = c.job_A; B.job_kT = c.job_kT; }
-      B.raw = cv.take<double>((size_t)c.max_jobs * GL);
-      c.order = cv.take<int>(c.ncap);
-      B.order = do_sort ? c.order : nullptr;
-      B.seg = split_below ? c.sl.seg : nullptr;
-      B.lvl_cnt = c.sl.lvl_cnt;
-      B.next_task = c.sl.next_task;
-      B.overflow = c.sl.overflow;
-      if (cv.p > cv.end)
-        return fail(NDPP_ENOMEM, "workspace carve overran (%zu > %zu)",
-                    (size_t)(cv.p - g_ws.base), g_ws.bytes);
-      c.chunk_ein = std::max<long>(1, c.max_jobs / rows_per_ein);
-      if (pl.cap_ein) c.chunk_ein = std::min<long>(c.chunk_ein, pl.cap_ein);
-    }
-  }
-  // (events of a chunk that an error path leaves behind)
-  struct EventSweep {
-    std::vector<FgCtx>& v;
-    ~EventSweep() {
-      for (auto& c : v) {
-        for (auto& e : c.ev) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
-        for (auto& e : c.gev) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
-      }
-    }
-  } sweep{ctx};
-  // whatever path leaves this function, nothing may still be running in the arena
-  struct Drain {
-    hipStream_t first;
-    hipStream_t* more;
-    int n_more;
-    ~Drain() {
-      (void)hipStreamSynchronize(first);
-      for (int k = 0; k < n_more; ++k) (void)hipStreamSynchronize(more[k]);
-    }
-  } drain{stream, g_ws.aux, side_by_side ? nctx - 1 : 0};
-
-  double mu_sum_ms = 0.0, gauss_sum_ms = 0.0;
-  double level_ms[32] = {0};
-  int mu_launches = 0;
-  std::vector<std::pair<float, float>> mu_spans;   // (start, end) of each fg_mu_kernel, ms after ev0
-
-  // queue one chunk of a context on its stream (nothing here waits for the device)
-  auto enqueue = [&](FgCtx& c) -> int {
-    FgBatch& B = c.B;
-    hipStream_t s = c.sl.s;
-    const bool sp = c.strict;
-    for (;;) {
-      c.this_ein = std::min<long>(c.chunk_ein, c.n - c.done);
-      B.n_jobs = joint ? (int)c.this_ein : (int)(c.this_ein * rows_per_ein);
-      const int ntrees = B.n_trees();
-      if ((long)ntrees * kSegPerGroup <= (long)B.tcap && ntrees <= c.ncap) break;
-      // more roots than the arena can even start with: take fewer energies
-      if (c.chunk_ein <= 1) return fail(NDPP_EOVERFLOW, "arena of %d nodes is too small for one E_in", c.ncap);
-      c.chunk_ein = std::max<long>(1, c.chunk_ein / 2);
-    }
-    HIP_TRY(hipMemsetAsync(c.sl.lvl_cnt, 0, (kMaxLevels + 2) * sizeof(int), s));
-    HIP_TRY(hipMemsetAsync(c.sl.next_task, 0, 2 * (kMaxLevels + 2) * sizeof(int), s));
-    HIP_TRY(hipMemsetAsync(c.sl.overflow, 0, sizeof(int), s));
-    hipLaunchKernelGGL(fg_set_int_kernel, dim3(1), dim3(1), 0, s, c.sl.lvl_cnt, B.n_trees());
-    hipLaunchKernelGGL(make_jobs_kernel, dim3(gs_blocks(B.n_jobs)), dim3(256), 0, s,
-                       B.n_jobs, rows_per_ein, joint, c.list + (size_t)c.done * c.lstride, c.lstride,
-                       ein_d, row_lo_d, c.job_ein, c.job_row, na ? na->nuc_of_ein : nullptr,
-                       na ? na->A : nullptr, na ? na->kT : nullptr, c.job_A, c.job_kT);
-    int rc = NDPP_OK;
-    if (sp) { rc = launch_fg_setup_strict(&B, sizeof B, s); if (rc) return rc; }
-    else launch_fg_setup(B, s);
-    const int nlev = B.eout_its + 1;
-    for (int level = 0; level < nlev; ++level) {
-      // the mu limits come out of Brent iterations that stop at a tolerance: in the product
-      // arithmetic they would end ~1e-7 away from the reference's, and every inner integral
-      // with them.  So the prep stage of every batch runs in the reference arithmetic
-      // (fg_strict_stages.hip; 0.2 % of a pass).
-      B.mu_nodes = nullptr;
-      rc = launch_fg_prep_strict(&B, sizeof B, level, s);
-      if (rc) return rc;
-      if (B.t_gl) {
-        hipEvent_t ga, gb;
-        HIP_TRY(hipEventCreate(&ga));
-        HIP_TRY(hipEventCreate(&gb));
-        c.gev.emplace_back(ga, gb);
-        HIP_TRY(hipEventRecord(ga, s));
-        launch_gauss_any(B, level, g_ws.num_cu, gauss_phased, s);
-        HIP_TRY(hipEventRecord(gb, s));
-      }
-      if (do_sort) {
-        // nodes sorted by weight class and the orders still active in any row; nodes with nothing
-        // left for the walk last (fg_node_bucket)
-        B.mu_nodes = c.sl.mu_nodes;
-        HIP_TRY(hipMemsetAsync(c.sl.mask_hist, 0, sizeof(int) * nb_sort, s));
-        hipLaunchKernelGGL(fg_sort_count_kernel, dim3(1024), dim3(256), 0, s, B, level, nb_sort, c.sl.mask_hist);
-        hipLaunchKernelGGL(fg_sort_scan_kernel, dim3(1), dim3(256), 0, s, c.sl.mask_hist, nb_sort, c.sl.mu_nodes);
-        hipLaunchKernelGGL(fg_sort_scatter_kernel, dim3(1024), dim3(256), 0, s, B, level, nb_sort,
-                           c.sl.mask_hist, c.order);
-      }
-      int* counter = c.sl.next_task + level;
-      if (B.seg) {
-        if (sp) { rc = launch_fg_seg_zero_strict(&B, sizeof B, level, s); if (rc) return rc; }
-        else launch_fg_seg_zero(B, level, s);
-      }
-      hipEvent_t a, b;
-      HIP_TRY(hipEventCreate(&a));
-      HIP_TRY(hipEventCreate(&b));
-      c.ev.emplace_back(a, b);
-      HIP_TRY(hipEventRecord(a, s));
-      if (sp) {
-        rc = launch_fg_mu_strict(&B, sizeof B, level, g_ws.num_cu, c.sl.gstack, counter, s);
-        if (rc) return rc;
-      } else {
-        launch_mu_any(B, level, g_ws.num_cu, c.sl.gstack, counter, s);
-      }
-      HIP_TRY(hipEventRecord(b, s));
-      if (sp) { rc = launch_fg_combine_strict(&B, sizeof B, level, s); if (rc) return rc; }
-      else launch_fg_combine(B, level, s);
-      B.mu_nodes = nullptr;
-      if (sp) { rc = launch_fg_node_strict(&B, sizeof B, level, s); if (rc) return rc; }
-      else launch_fg_node(B, level, s);
-    }
-    for (int level = nlev - 1; level >= 0; --level) {
-      if (sp) { rc = launch_fg_reduce_strict(&B, sizeof B, level, s); if (rc) return rc; }
-      else launch_fg_reduce(B, level, s);
-    }
-    if (sp) { rc = launch_fg_assemble_strict(&B, sizeof B, s); if (rc) return rc; }
-    else launch_fg_assemble(B, s);
-    const int* lst = c.list + (size_t)c.done * c.lstride;
-    if (rows_per_ein == 2)
-      hipLaunchKernelGGL(blend_kernel, dim3(gs_blocks(c.this_ein * GL)), dim3(256), 0, s,
-                         (int)c.this_ein, lst, c.lstride, B.raw, w_hi_d, GL, out_d);
-    else
-      hipLaunchKernelGGL(copy_raw_kernel, dim3(gs_blocks(c.this_ein * GL)), dim3(256), 0, s,
-                         (int)c.this_ein, lst, c.lstride, B.raw, GL, out_d);
-    c.inflight = true;
-    return NDPP_OK;
-  };
-
-  // the chunk of a context has left the device: its timings, and whether it has to be redone
-  auto retire = [&](FgCtx& c) -> int {
-    c.inflight = false;
-    int ovf = 0;
-    HIP_TRY(hipMemcpyAsync(&ovf, c.sl.overflow, sizeof(int), hipMemcpyDeviceToHost, c.sl.s));
-    HIP_TRY(hipStreamSynchronize(c.sl.s));
-    HIP_TRY(hipGetLastError());
-    int lvl_i = 0;
-    const int ev_per_level = 1;
-    for (auto& e : c.ev) {
-      float t0 = 0.f, t1 = 0.f;
-      if (hipEventElapsedTime(&t0, ev0, e.first) == hipSuccess &&
-          hipEventElapsedTime(&t1, ev0, e.second) == hipSuccess) {
-        mu_sum_ms += t1 - t0;
-        if (lvl_i / ev_per_level < 32) level_ms[lvl_i / ev_per_level] += t1 - t0;
-        mu_spans.emplace_back(t0, t1);
-      }
-      lvl_i++;
-      mu_launches++;
-      (void)hipEventDestroy(e.first);
-      (void)hipEventDestroy(e.second);
-    }
-    c.ev.clear();
-    for (auto& e : c.gev) {
-      // (the Gauss stage of a level is part of its inner integration: counted in mu_busy_ms)
-      float t0 = 0.f, t1 = 0.f;
-      if (hipEventElapsedTime(&t0, ev0, e.first) == hipSuccess &&
-          hipEventElapsedTime(&t1, ev0, e.second) == hipSuccess) {
-        gauss_sum_ms += t1 - t0;
-        mu_spans.emplace_back(t0, t1);
-      }
-      (void)hipEventDestroy(e.first);
-      (void)hipEventDestroy(e.second);
-    }
-    c.gev.clear();
-    if (ovf) {
-      // the adaptive trees outgrew the arena: redo this chunk with half the energies
-      if (c.chunk_ein <= 1)
-        return fail(NDPP_EOVERFLOW, "outer tree of one E_in exceeds %d nodes", c.ncap);
-      c.chunk_ein = std::max<long>(1, c.chunk_ein / 2);
-    } else {
-      c.done += c.this_ein;
-    }
-    return NDPP_OK;
-  };
-
-  if (side_by_side) {
-    for (auto& c : ctx) { rc = enqueue(c); if (rc) return rc; }
-    for (;;) {
-      int live = 0;
-      bool moved = false;
-      for (auto& c : ctx) {
-        if (!c.inflight) continue;
-        ++live;
-        const hipError_t q = hipStreamQuery(c.sl.s);
-        if (q == hipErrorNotReady) continue;
-        if (q != hipSuccess) return fail(NDPP_EDEVICE, "free-gas pipeline failed: %s", hipGetErrorString(q));
-        rc = retire(c);
-        if (rc) return rc;
-        if (c.done < c.n) { rc = enqueue(c); if (rc) return rc; }
-        moved = true;
-      }
-      if (!live) break;
-      if (!moved) std::this_thread::sleep_for(std::chrono::microseconds(50));
-    }
-  } else {
-    for (auto& c : ctx)
-      while (c.done < c.n) {
-        rc = enqueue(c);
-        if (!rc) rc = retire(c);
-        if (rc) return rc;
-      }
-  }
-  // time during which at least one fg_mu_kernel was in flight
-  double mu_ms = 0.0;
-  {
-    std::sort(mu_spans.begin(), mu_spans.end());
-    float end = -1.f;
-    for (auto& sp : mu_spans) {
-      if (sp.second <= end) continue;
-      mu_ms += sp.second - std::max(sp.first, end);
-      end = sp.second;
-    }
-  }
-
+  if ((rc = carve_contexts(ctx, side_by_side, a, t, pl, h, cv, gauss_on, g_ws))) return rc;
+  // (after everything that owns events, inside the workspace lock: runs first on the way out)
+  Drain drain{stream, g_ws.aux, side_by_side ? nctx - 1 : 0};
+  if ((rc = run_contexts(ctx, side_by_side, a, t, pl, tm))) return rc;
   if (status_d)
-    hipLaunchKernelGGL(status_kernel, dim3(gs_blocks(n_ein)), dim3(256), 0, stream, n_ein, ein_d,
-                       out_d, GL, row_lo_d, n_rows, rows_per_ein, status_d);
-  HIP_TRY(hipEventRecord(ev1, stream));
+    hipLaunchKernelGGL(status_kernel, dim3(gs_blocks(n_ein)), dim3(256), 0, stream, n_ein, ein_d, out_d, a.GL(),
+                       row_lo_d, n_rows, rows_per_ein, status_d);
+  HIP_TRY(tm.ev1.record(stream));
   unsigned long long hs[kNumStats];
-  HIP_TRY(hipMemcpyAsync(hs, dstats, sizeof(hs), hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipMemcpyAsync(hs, h.dstats, sizeof(hs), hipMemcpyDeviceToHost, stream));
   HIP_TRY(hipStreamSynchronize(stream));
   HIP_TRY(hipGetLastError());
-  {
-    float ms = 0.f, ms4 = 0.f;
-    if (hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess) ndpp::g_last_gpu_ms = ms;
-    // the span up to ev_f4 is classification + the file4 kernel; the rest is the free-gas pipeline
-    if (hipEventElapsedTime(&ms4, ev0, ev_f4) == hipSuccess) {
-      profile_add(kProfFile4, ms4);
-      profile_add(kProfFreegasMu, mu_ms);
-      profile_add(kProfFreegasOther, std::max(0.0, (double)ms - ms4 - mu_ms));
-    }
-  }
-  if (stats) {
-    stats->k_evals = hs[kStatKEvals];
-    stats->mu_visits = hs[kStatMuVisits];
-    stats->mu_integrals = hs[kStatMuIntegrals];
-    stats->eout_nodes = hs[kStatEoutNodes];
-    stats->wave_iters = hs[kStatWaveIters];
-    stats->lane_iters = hs[kStatLaneIters];
-    stats->order_visits = hs[kStatOrderVisits];
-    stats->gauss_integrals = hs[kStatGaussIntegrals];
-    stats->gauss_ms = gauss_sum_ms;
-    for (int k = 0; k < 32; ++k) stats->mu_level_ms[k] = level_ms[k];
-    stats->mu_kernel_ms = mu_sum_ms;
-    stats->mu_busy_ms = mu_ms;
-    stats->mu_kernel_launches = mu_launches;
-    stats->contexts = side_by_side ? nctx : 1;
-    float ms = 0.f;
-    hipEventElapsedTime(&ms, ev0, ev1);
-    stats->total_ms = ms;
-  }
+  tm.publish(hs, side_by_side ? nctx : 1, stats);
   return NDPP_OK;
 }
 
@@ -1152,51 +1193,30 @@ int run_batch_h(const ndpp_params* p, double A, double kT, double cutoff, double
   if (n_ein == 0) return NDPP_OK;
   if (!ein || !row_lo || !f_tab || !e_bins || (!out && !sink) || (rows_per_ein == 2 && !w_hi))
     return fail(NDPP_EINVAL, "NULL array argument");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-    return fail(NDPP_EDEVICE, "no HIP device available (libndpp_hip has no CPU path)");
-  const int L = p->order, M = p->mu_bins;
-  const size_t GL = (size_t)G * L;
-  double *ein_d = nullptr, *w_d = nullptr, *f_d = nullptr, *eb_d = nullptr, *out_d = nullptr;
-  int *row_d = nullptr, *st_d = nullptr;
-  auto cleanup = [&]() {
-    dev_free(ein_d); dev_free(w_d); dev_free(f_d); dev_free(eb_d); dev_free(out_d);
-    dev_free(row_d); dev_free(st_d);
-  };
-#define TRY_OR_CLEAN(expr)                                                     \
-  do {                                                                         \
-    hipError_t e_ = (expr);                                                    \
-    if (e_ != hipSuccess) {                                                    \
-      cleanup();                                                               \
-      return fail(NDPP_EDEVICE, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-    }                                                                          \
-  } while (0)
-  TRY_OR_CLEAN(dev_alloc((void**)&ein_d, sizeof(double) * n_ein));
-  TRY_OR_CLEAN(dev_alloc((void**)&w_d, sizeof(double) * n_ein));
-  TRY_OR_CLEAN(dev_alloc((void**)&row_d, sizeof(int) * n_ein));
-  TRY_OR_CLEAN(dev_alloc((void**)&st_d, sizeof(int) * n_ein));
-  TRY_OR_CLEAN(dev_alloc((void**)&f_d, sizeof(double) * (size_t)n_rows * M));
-  TRY_OR_CLEAN(dev_alloc((void**)&eb_d, sizeof(double) * (G + 1)));
-  TRY_OR_CLEAN(dev_alloc((void**)&out_d, sizeof(double) * n_ein * GL));
-  TRY_OR_CLEAN(hipMemcpy(ein_d, ein, sizeof(double) * n_ein, hipMemcpyHostToDevice));
-  if (w_hi) TRY_OR_CLEAN(hipMemcpy(w_d, w_hi, sizeof(double) * n_ein, hipMemcpyHostToDevice));
-  TRY_OR_CLEAN(hipMemcpy(row_d, row_lo, sizeof(int) * n_ein, hipMemcpyHostToDevice));
-  TRY_OR_CLEAN(hipMemcpy(f_d, f_tab, sizeof(double) * (size_t)n_rows * M, hipMemcpyHostToDevice));
-  TRY_OR_CLEAN(hipMemcpy(eb_d, e_bins, sizeof(double) * (G + 1), hipMemcpyHostToDevice));
-  rc = run_batch_d(p, A, kT, cutoff, Q, n_ein, ein_d, row_d, w_d, n_rows, f_d, G, eb_d,
-                   out_d, st_d, rows_per_ein, nullptr, stats);
-  if (rc == NDPP_OK && sink) {
-    rc = sink->consume(out_d, n_ein, GL);
-    if (rc == NDPP_OK) TRY_OR_CLEAN(hipDeviceSynchronize());
+  if ((rc = require_device())) return rc;
+  const size_t GL = (size_t)G * p->order, M = (size_t)p->mu_bins;
+  // (every error below returns through fail(), which waits for the device before these go back to the cache)
+  DevBuf<double> ein_d, w_d, f_d, eb_d, out_d;
+  DevBuf<int> row_d, st_d;
+  HIP_TRY(ein_d.upload(ein, n_ein));
+  HIP_TRY(w_d.upload(w_hi, n_ein));              // (no w_hi: allocated only)
+  HIP_TRY(row_d.upload(row_lo, n_ein));
+  HIP_TRY(st_d.alloc(n_ein));
+  HIP_TRY(f_d.upload(f_tab, (size_t)n_rows * M));
+  HIP_TRY(eb_d.upload(e_bins, G + 1));
+  HIP_TRY(out_d.alloc(n_ein * GL));
+  rc = run_batch_d(p, A, kT, cutoff, Q, n_ein, ein_d.p, row_d.p, w_d.p, n_rows, f_d.p, G, eb_d.p,
+                   out_d.p, st_d.p, rows_per_ein, nullptr, stats);
+  if (rc) return rc;
+  if (sink) {
+    rc = sink->consume(out_d.p, n_ein, GL);
+    if (rc) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+  } else {
+    HIP_TRY(out_d.download(out, n_ein * GL));
   }
-  if (rc == NDPP_OK) {
-    if (!sink) TRY_OR_CLEAN(hipMemcpy(out, out_d, sizeof(double) * n_ein * GL, hipMemcpyDeviceToHost));
-    if (status)
-      TRY_OR_CLEAN(hipMemcpy(status, st_d, sizeof(int) * n_ein, hipMemcpyDeviceToHost));
-  }
-  cleanup();
-  return rc;
-#undef TRY_OR_CLEAN
+  if (status) HIP_TRY(st_d.download(status, n_ein));
+  return NDPP_OK;
 }
 
 int check_mu_grid(const ndpp_params* p, const double* mu) {
@@ -1295,9 +1315,7 @@ int ndpp_dev_synchronize(void) {
 }
 
 int ndpp_reserve_workspace(size_t bytes) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-    return fail(NDPP_EDEVICE, "no HIP device available (libndpp_hip has no CPU path)");
+  if (int rc = require_device()) return rc;
   Workspace* ws = nullptr;
   int rc = current_workspace(&ws);
   if (rc) return rc;
@@ -1356,9 +1374,8 @@ int ndpp_freegas_rough_rows(int mu_bins, int n_rows, const double* f_tab, int* r
 }
 
 int ndpp_set_device(int device) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-    return fail(NDPP_EDEVICE, "no HIP device available (libndpp_hip has no CPU path)");
+  if (int rc = require_device()) return rc;
+  const int ndev = ndpp_device_count();
   if (device < 0 || device >= ndev) return fail(NDPP_EINVAL, "device %d outside 0..%d", device, ndev - 1);
   HIP_TRY(hipSetDevice(device));
   return NDPP_OK;
@@ -1411,9 +1428,7 @@ int ndpp_elastic_leg_batch_d(const ndpp_params* p, double A, double kT,
                              const double* w_hi_d, int n_rows, const double* f_tab_d,
                              int G, const double* e_bins_d, double* out_d,
                              int* status_d, void* stream, ndpp_stats* stats) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-    return fail(NDPP_EDEVICE, "no HIP device available (libndpp_hip has no CPU path)");
+  if (int rc = require_device()) return rc;
   return run_batch_d(p, A, kT, freegas_cutoff, Q, n_ein, ein_d, row_lo_d, w_hi_d,
                      n_rows, f_tab_d, G, e_bins_d, out_d, status_d, 2,
                      (hipStream_t)stream, stats);
@@ -1425,9 +1440,7 @@ int ndpp_elastic_leg_multi_d(const ndpp_params* p, int n_nuc, const double* A_d,
                              const int* row_lo_d, const double* w_hi_d, int n_rows,
                              const double* f_tab_d, int G, const double* e_bins_d, double* out_d,
                              int* status_d, void* stream, ndpp_stats* stats) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-    return fail(NDPP_EDEVICE, "no HIP device available (libndpp_hip has no CPU path)");
+  if (int rc = require_device()) return rc;
   if (n_nuc < 1 || !A_d || !kT_d || !cutoff_d || !Q_d || (n_ein > 0 && !nuc_of_ein_d))
     return fail(NDPP_EINVAL, "n_nuc=%d or NULL per-nuclide array", n_nuc);
   const NucArrays na{n_nuc, A_d, kT_d, cutoff_d, Q_d, nuc_of_ein_d};
@@ -1447,44 +1460,27 @@ int ndpp_elastic_leg_multi(const ndpp_params* p, int n_nuc, const double* A, con
   if (n_ein == 0) return NDPP_OK;
   if (!A || !kT || !freegas_cutoff || !Q || !ein || !nuc_of_ein || !row_lo || !w_hi || !f_tab || !e_bins || !out)
     return fail(NDPP_EINVAL, "NULL array argument");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-    return fail(NDPP_EDEVICE, "no HIP device available (libndpp_hip has no CPU path)");
+  if ((rc = require_device())) return rc;
   const size_t GL = (size_t)G * p->order, M = (size_t)p->mu_bins;
-  struct Buf {
-    void* p = nullptr;
-    ~Buf() { if (p) dev_free(p); }
-    hipError_t up(const void* h, size_t bytes) {
-      hipError_t e = dev_alloc(&p, bytes ? bytes : 8);
-      if (e != hipSuccess || !h) return e;
-      return hipMemcpy(p, h, bytes, hipMemcpyHostToDevice);
-    }
-  } dA, dkT, dcut, dQ, dein, dnuc, drow, dw, df, dbins, dout, dst;
-#define MULTI_TRY(expr)                                                           \
-  do {                                                                            \
-    hipError_t e_ = (expr);                                                       \
-    if (e_ != hipSuccess)                                                         \
-      return fail(NDPP_EDEVICE, "%s failed: %s", #expr, hipGetErrorString(e_));   \
-  } while (0)
-  MULTI_TRY(dA.up(A, sizeof(double) * n_nuc));
-  MULTI_TRY(dkT.up(kT, sizeof(double) * n_nuc));
-  MULTI_TRY(dcut.up(freegas_cutoff, sizeof(double) * n_nuc));
-  MULTI_TRY(dQ.up(Q, sizeof(double) * n_nuc));
-  MULTI_TRY(dein.up(ein, sizeof(double) * n_ein));
-  MULTI_TRY(dnuc.up(nuc_of_ein, sizeof(int) * n_ein));
-  MULTI_TRY(drow.up(row_lo, sizeof(int) * n_ein));
-  MULTI_TRY(dw.up(w_hi, sizeof(double) * n_ein));
-  MULTI_TRY(df.up(f_tab, sizeof(double) * (size_t)n_rows * M));
-  MULTI_TRY(dbins.up(e_bins, sizeof(double) * (G + 1)));
-  MULTI_TRY(dout.up(nullptr, sizeof(double) * n_ein * GL));
-  MULTI_TRY(dst.up(nullptr, sizeof(int) * n_ein));
-  rc = ndpp_elastic_leg_multi_d(p, n_nuc, (double*)dA.p, (double*)dkT.p, (double*)dcut.p,
-                                (double*)dQ.p, n_ein, (double*)dein.p, (int*)dnuc.p, (int*)drow.p,
-                                (double*)dw.p, n_rows, (double*)df.p, G, (double*)dbins.p,
-                                (double*)dout.p, (int*)dst.p, nullptr, stats);
+  DevBuf<double> dA, dkT, dcut, dQ, dein, dw, df, dbins, dout;
+  DevBuf<int> dnuc, drow, dst;
+  HIP_TRY(dA.upload(A, n_nuc));
+  HIP_TRY(dkT.upload(kT, n_nuc));
+  HIP_TRY(dcut.upload(freegas_cutoff, n_nuc));
+  HIP_TRY(dQ.upload(Q, n_nuc));
+  HIP_TRY(dein.upload(ein, n_ein));
+  HIP_TRY(dnuc.upload(nuc_of_ein, n_ein));
+  HIP_TRY(drow.upload(row_lo, n_ein));
+  HIP_TRY(dw.upload(w_hi, n_ein));
+  HIP_TRY(df.upload(f_tab, (size_t)n_rows * M));
+  HIP_TRY(dbins.upload(e_bins, G + 1));
+  HIP_TRY(dout.alloc(n_ein * GL));
+  HIP_TRY(dst.alloc(n_ein));
+  rc = ndpp_elastic_leg_multi_d(p, n_nuc, dA.p, dkT.p, dcut.p, dQ.p, n_ein, dein.p, dnuc.p, drow.p, dw.p, n_rows,
+                                df.p, G, dbins.p, dout.p, dst.p, nullptr, stats);
   if (rc) return rc;
-  MULTI_TRY(hipMemcpy(out, dout.p, sizeof(double) * n_ein * GL, hipMemcpyDeviceToHost));
-  if (status) MULTI_TRY(hipMemcpy(status, dst.p, sizeof(int) * n_ein, hipMemcpyDeviceToHost));
+  HIP_TRY(dout.download(out, n_ein * GL));
+  if (status) HIP_TRY(dst.download(status, n_ein));
   return NDPP_OK;
 }
 
