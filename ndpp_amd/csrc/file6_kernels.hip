@@ -293,18 +293,8 @@ extern "C" int ndpp_file6_leg_batch(const ndpp_params* p, double awr, int frame_
                                     const double* eout, const double* pdf, const int* intt,
                                     const double* f, int G, const double* e_bins, double* out,
                                     int* status) {
-  return file6_leg_batch_sink(p, awr, frame_cm, n_ein, ein, row_lo, n_rows, e_grid, row_ptr, eout, pdf,
-                              intt, f, G, e_bins, out, status, nullptr);
-}
-
-int ndpp::file6_leg_batch_sink(const ndpp_params* p, double awr, int frame_cm, int n_ein,
-                               const double* ein, const int* row_lo, int n_rows,
-                               const double* e_grid, const int* row_ptr,
-                               const double* eout, const double* pdf, const int* intt,
-                               const double* f, int G, const double* e_bins, double* out,
-                               int* status, DeviceSink* sink, const double* f_dev) {
   return file6_batch_sink(p, awr, frame_cm, n_ein, ein, row_lo, n_rows, e_grid, row_ptr, eout, pdf, intt, f, G,
-                          e_bins, 0, out, status, sink, f_dev);
+                          e_bins, 0, out, status, nullptr);
 }
 
 // n_tab = 0: the Legendre moments (L = p->order per group); n_tab > 0: the tabular bins

@@ -70,20 +70,18 @@ int elastic_leg_batch_sink(const ndpp_params* p, double A, double kT, double fre
                            int n_ein, const double* ein, const int* row_lo, const double* w_hi,
                            int n_rows, const double* f_tab, int G, const double* e_bins, double* out,
                            int* status, DeviceSink* sink);
-// (f_dev non-null: the table f[sum NP][M] is already on the device -- convert_distro_keep -- and `f`
-// is not read)
-int file6_leg_batch_sink(const ndpp_params* p, double awr, int frame_cm, int n_ein, const double* ein,
-                         const int* row_lo, int n_rows, const double* e_grid, const int* row_ptr,
-                         const double* eout, const double* pdf, const int* intt, const double* f, int G,
-                         const double* e_bins, double* out, int* status, DeviceSink* sink,
-                         const double* f_dev = nullptr);
-// file6_leg_batch_sink with n_tab: n_tab > 0 gives the tabular bins of ndpp_file6_tab_batch, n_tab per
-// group; n_tab = 0 the Legendre moments
+// n_tab = 0: the Legendre moments of ndpp_file6_leg_batch; n_tab > 0: the tabular bins of
+// ndpp_file6_tab_batch, n_tab per group.  (f_dev non-null: the table f[sum NP][M] is already on the
+// device -- convert_distro_keep -- and `f` is not read)
 int file6_batch_sink(const ndpp_params* p, double awr, int frame_cm, int n_ein, const double* ein,
                      const int* row_lo, int n_rows, const double* e_grid, const int* row_ptr,
                      const double* eout, const double* pdf, const int* intt, const double* f, int G,
                      const double* e_bins, int n_tab, double* out, int* status, DeviceSink* sink,
                      const double* f_dev = nullptr);
+int law9_leg_batch_sink(const ndpp_params* p, int n_ein, const double* ein, const int* row_lo,
+                        const double* w_hi, int n_rows, const double* f_tab, int n_edata,
+                        const double* edata, int G, const double* e_bins, double* out, int* status,
+                        DeviceSink* sink);
 // tab_kernels.hip: the tabular counterparts of elastic_leg_batch_sink and law9_leg_batch_sink
 int elastic_tab_batch_sink(const ndpp_params* p, double A, double kT, double freegas_cutoff, double Q,
                            int n_ein, const double* ein, const int* row_lo, const double* w_hi,
@@ -111,10 +109,6 @@ int convert_distro_keep(int mu_bins, const ndpp_ace_reaction* r, int G, const do
                         int total_np, double* e_grid, int* row_ptr, double* eout, double* pdf,
                         double* cdf, int* intt, double** f_dev);
 void free_converted(double* f_dev);
-int law9_leg_batch_sink(const ndpp_params* p, int n_ein, const double* ein, const int* row_lo,
-                        const double* w_hi, int n_rows, const double* f_tab, int n_edata,
-                        const double* edata, int G, const double* e_bins, double* out, int* status,
-                        DeviceSink* sink);
 // dst[where[k]][j] += src[k][j] * scale[k] * pv[k]; nudst[where[k]][j] += yield[k] * that
 // (scatt_interp_distro's scaling and calc_inelastic_grid's reaction sum, scattdata_header.F90:496,
 // scatt.F90:753,:762, in their order of operations; all pointers device; null stream)

@@ -1,18 +1,24 @@
 // nuclide.hip -- host-only orchestration of one nuclide: calc_scatt (scatt.F90:33-157)
-// behind the C ABI, for hosts that are not the reference's Fortran.
+// behind the C ABI, for hosts that are not the reference's Fortran.  scatt_nuclide_impl is the
+// sequence of its steps:
 //
-//   ScattData%init + convert_distro      -> ndpp_scattdata_shape / ndpp_convert_distro
-//   cutoff / inelastic threshold         -> scatt.F90:103-123
-//   create_Ein_grid                      -> ndpp_create_ein_grid
-//   calc_elastic_grid   (:603-675)       -> bookkeeping here + ndpp_elastic_leg_batch
-//   calc_inelastic_grid (:682-778)       -> bookkeeping here + ndpp_elastic_leg_batch /
-//                                           ndpp_file6_leg_batch / ndpp_law9_leg_batch
+//   read_hooks              the NDPP_HIP_* hooks of this file, once per call
+//   convert_reactions       ScattData%init + convert_distro -> ndpp_scattdata_shape / ndpp_convert_distro
+//   cutoff_and_threshold    scatt.F90:103-123
+//   make_grids              create_Ein_grid -> ndpp_create_ein_grid (or the caller's lists); the result
+//   run_grid, per grid      calc_elastic_grid (:603-675) / calc_inelastic_grid (:682-778):
+//     select_energies, select_yields   the bookkeeping of one reaction
+//     integrate_reaction               integrate_distro's dispatch over the batch calls
+//     ElasticAssign / HostSum / DeviceSum   take() a reaction's moments, finish() the grid
+//     copy_top_rows
 // "Bookkeeping" is scatt_interp_distro (scattdata_header.F90:391-499): threshold and
 // top-of-grid tests, the cross-section interpolation, the row search with the
 // duplicate-row skip, p_valid, and after the batch call the sigma * p_valid scaling,
 // the reaction sum and the nu-scatter yield (scatt.F90:745-762) in the reference's
-// order of operations.  fortran/ndpp_hip_mod.f90 holds the same logic for the
-// Fortran host; both are checked against the reference's calc_scatt.
+// order of operations.  ElasticDefer (append_reaction, run_elastic_defer) collects angular-only
+// reactions for one ndpp_elastic_leg_multi call: a library's elastic grids, a host-summed grid's
+// levels.  fortran/ndpp_hip_mod.f90 holds the same logic for the Fortran host; both are checked
+// against the reference's calc_scatt.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -30,20 +36,38 @@
 namespace ndpp {
 namespace {
 
+// The NDPP_HIP_* hooks of the whole-nuclide driver, each with its default and meaning (INTEGRATION.md
+// section 6); read once per scatt_nuclide_impl call, here and nowhere else.
+struct Hooks {
+  bool device_tables = true;              // NDPP_HIP_NO_DEVICE_TABLES=1 (test): every table through the host
+  bool level_batch = true;                // NDPP_HIP_NO_LEVEL_BATCH=1 (test): one batch call per level
+  size_t dev_sum_min = (size_t)1 << 20;   // NDPP_HIP_DEV_SUM_MIN=n (test): see run_grid
+  bool host_timing = false;               // NDPP_HIP_HOST_TIMING=1: HostClock's line on stderr
+};
+Hooks read_hooks() {
+  const auto is_one = [](const char* name) { const char* e = getenv(name); return e && e[0] == '1'; };
+  Hooks h;
+  h.device_tables = !is_one("NDPP_HIP_NO_DEVICE_TABLES");
+  h.level_batch = !is_one("NDPP_HIP_NO_LEVEL_BATCH");
+  if (const char* e = getenv("NDPP_HIP_DEV_SUM_MIN")) h.dev_sum_min = (size_t)atoll(e);
+  h.host_timing = is_one("NDPP_HIP_HOST_TIMING");
+  return h;
+}
 
-// NDPP_HIP_HOST_TIMING=1: where the host side of one nuclide spends its time (stderr)
+// Hooks::host_timing: where the host side of one nuclide spends its time (stderr)
 struct HostClock {
   using clk = std::chrono::steady_clock;
+  bool print;
   clk::time_point t0 = clk::now();
   double acc[6] = {0, 0, 0, 0, 0, 0};   // convert, grids + matrices, bookkeeping, batch calls, reaction sum, top rows
+  explicit HostClock(bool on) : print(on) {}
   void lap(int k) {
     const clk::time_point t = clk::now();
     acc[k] += std::chrono::duration<double, std::milli>(t - t0).count();
     t0 = t;
   }
   ~HostClock() {
-    const char* e = getenv("NDPP_HIP_HOST_TIMING");
-    if (e && e[0] == '1')
+    if (print)
       fprintf(stderr, "ndpp_scatt_nuclide host ms: convert %.1f  grids+matrices %.1f  bookkeeping %.1f  "
                       "batch calls %.1f  reaction sum / download %.1f  top rows %.1f\n",
               acc[0], acc[1], acc[2], acc[3], acc[4], acc[5]);
@@ -226,142 +250,158 @@ struct RxnState {
   double fab_energy[2];
 };
 
-}  // namespace
-}  // namespace ndpp
-
-using namespace ndpp;
-
-extern "C" void ndpp_free_scatt_result(ndpp_scatt_result* r) {
-  if (!r) return;
-  free(r->ein_el); free(r->ein_inel); free(r->el_mat); free(r->inel_mat); free(r->nuinel_mat);
-  memset(r, 0, sizeof(*r));
-}
-
-// n_tab = 0: Legendre moments (L = p->order); n_tab > 0: calc_scatt with scatt_type = tabular,
-// n_tab lab-cosine bins per group (the tabular batch calls; no deferred or level batches)
-static int scatt_nuclide_impl(const ndpp_params* p, const ndpp_ace_nuclide* nuc, int n_bins,
-                              const double* e_bins, int nuscatt, ndpp_scatt_result* out,
-                              ElasticDefer* defer, int n_tab = 0, const GivenGrids* given = nullptr) {
-  if (!p || !nuc || !e_bins || !out) return fail(NDPP_EINVAL, "NULL argument");
-  memset(out, 0, sizeof(*out));
-  if (n_tab < 0 || n_tab > NDPP_MAX_TAB_BINS)
-    return fail(NDPP_EINVAL, "n_tab=%d outside 1..%d", n_tab, NDPP_MAX_TAB_BINS);
-  if (n_tab > 0 && defer)
-    return fail(NDPP_EINVAL, "tabular output has no deferred (mixed-nuclide) elastic batch");
-  if (n_bins < 2) return fail(NDPP_EINVAL, "need at least one group");
-  if (nuc->n_grid < 2 || !nuc->energy || !nuc->elastic)
-    return fail(NDPP_EINVAL, "nuclide energy grid / elastic cross section missing");
-  if (nuc->n_reaction < 1 || !nuc->reactions) return fail(NDPP_EINVAL, "nuclide has no reactions");
-  const int G = n_bins - 1, L = n_tab > 0 ? n_tab : p->order, M = p->mu_bins;
-  const double Etop = e_bins[G];
-  int rc;
+// what the steps of one scatt_nuclide_impl call share
+struct Call {
+  const ndpp_params* p;
+  const ndpp_ace_nuclide* nuc;
+  int n_bins;
+  const double* e_bins;
+  int n_tab, G, L, M;     // n_tab = 0: L = p->order Legendre moments; n_tab > 0: L = n_tab bins
+  size_t GL;
+  double Etop;
+  Hooks hooks;
   HostClock hc;
+  Call(const ndpp_params* p_, const ndpp_ace_nuclide* nuc_, int n_bins_, const double* e_bins_, int n_tab_)
+      : p(p_), nuc(nuc_), n_bins(n_bins_), e_bins(e_bins_), n_tab(n_tab_), G(n_bins_ - 1),
+        L(n_tab_ > 0 ? n_tab_ : p_->order), M(p_->mu_bins), GL((size_t)G * L), Etop(e_bins_[G]),
+        hooks(read_hooks()), hc(hooks.host_timing) {}
+};
 
-  // ---- init + convert_distro for every reaction and nested distribution (:59-106)
-  std::vector<SD> sds;
-  std::vector<RxnState> st((size_t)nuc->n_reaction);
+// ---- init + convert_distro for every reaction and nested distribution (:59-106)
+
+// the Reaction as the next ScattData%init sees it: rx, with what an earlier init rewrote on it
+ndpp_ace_reaction reaction_view(const ndpp_ace_nuclide* nuc, const ndpp_ace_rxn& rx, const ndpp_ace_edist* ed,
+                                const RxnState& st) {
   const static int kIso[2] = {1, 1}, kZero[2] = {0, 0};
   const static double kZeroD[2] = {0.0, 0.0};
+  ndpp_ace_reaction a;
+  memset(&a, 0, sizeof(a));
+  a.MT = rx.MT;
+  a.law = ed ? ed->law : 0;
+  a.threshold_energy = nuc->energy[rx.threshold - 1];
+  if (st.has_angle_dist) {
+    a.has_angle_dist = 1;
+    if (st.fabricated) {   // the isotropic adist an earlier init wrote into rxn%adist
+      a.n_adist = 2; a.adist_energy = st.fab_energy; a.adist_type = kIso;
+      a.adist_location = kZero; a.n_adist_data = 2; a.adist_data = kZeroD;
+    } else {
+      a.n_adist = rx.n_adist; a.adist_energy = rx.adist_energy; a.adist_type = rx.adist_type;
+      a.adist_location = rx.adist_location; a.n_adist_data = rx.n_adist_data;
+      a.adist_data = rx.adist_data;
+    }
+  }
+  if (ed) { a.n_edata = ed->n_data; a.edata = ed->data; }
+  return a;
+}
+
+// what init leaves behind (:135-223): on the ScattData, and on the reaction for the inits after it
+void after_init(const Call& c, const ndpp_ace_edist* ed, double threshold_energy, SD* sd, RxnState* st) {
+  const bool had_adist = st->has_angle_dist;
+  if (had_adist) {
+    sd->has_adist = true;
+    sd->has_edist = ed && ed->law != 3;
+  } else if (ed) {
+    if (ed->law == 4 || ed->law == 3 || ed->law == 9) {
+      sd->has_adist = true;
+      sd->has_edist = (ed->law == 9 || ed->law == 4);
+    } else {
+      sd->has_edist = true;
+    }
+  } else {
+    sd->has_adist = true;
+    st->in_cm = true;   // :218
+  }
+  if (!had_adist && sd->has_adist) {      // rxn%adist now holds the isotropic table
+    st->has_angle_dist = true;
+    st->fabricated = true;
+    st->fab_energy[1] = c.Etop;
+    st->fab_energy[0] = (threshold_energy > c.e_bins[0]) ? threshold_energy : c.e_bins[0];
+  }
+  sd->edist = sd->has_edist ? ed : nullptr;
+}
+
+// integrate_distro's dispatch (:533-656): 1 angular only, 2 file 6 in the CM, 3 law 9, 4 file 6 in the lab
+int distro_kind(const SD& sd) {
+  if (sd.has_adist && !sd.has_edist) return 1;
+  if (sd.in_cm) return 2;
+  if (sd.has_adist && sd.law == 9) return 3;
+  return 4;
+}
+
+// convert_distro: the table on the host, or kept on the device for the file-6 integrators
+int convert_table(const Call& c, const ndpp_ace_reaction& a, int NE, int tot, SD* sd) {
+  sd->NE = NE;
+  sd->e_grid.resize(NE); sd->row_ptr.resize(NE + 1); sd->intt.resize(NE);
+  sd->eout.resize(tot); sd->pdf.resize(tot); sd->cdf.resize(tot);
+  // angular-only tables (kind 1) go into host-side batches, law 9 reads column 1 of every row on
+  // the host; the rest is file 6 (in_cm, not yet known here, only chooses between kinds 2 and 4)
+  const bool file6_only = !(sd->has_adist && !sd->has_edist) && !(sd->has_adist && sd->law == 9);
+  if (file6_only && c.hooks.device_tables) {
+    double* fd = nullptr;
+    const int rc = convert_distro_keep(c.M, &a, c.G, c.e_bins, NE, tot, sd->e_grid.data(), sd->row_ptr.data(),
+                                       sd->eout.data(), sd->pdf.data(), sd->cdf.data(), sd->intt.data(), &fd);
+    sd->f_dev = std::shared_ptr<double>(fd, [](double* q) { free_converted(q); });
+    return rc;
+  }
+  sd->f.resize((size_t)tot * c.M);
+  return ndpp_convert_distro(c.M, &a, c.G, c.e_bins, NE, tot, sd->e_grid.data(), sd->row_ptr.data(),
+                             sd->eout.data(), sd->pdf.data(), sd->cdf.data(), sd->intt.data(), sd->f.data());
+}
+
+// every reaction's SD list; RxnState lives here, one per reaction
+int convert_reactions(const Call& c, std::vector<SD>* sds) {
+  const ndpp_ace_nuclide* nuc = c.nuc;
   for (int ir = 0; ir < nuc->n_reaction; ++ir) {
     const ndpp_ace_rxn& rx = nuc->reactions[ir];
     if (rx.threshold < 1 || rx.threshold > nuc->n_grid)
       return fail(NDPP_EINVAL, "reaction %d: threshold index %d outside the grid", ir, rx.threshold);
-    st[ir].has_angle_dist = rx.has_angle_dist != 0;
-    st[ir].in_cm = rx.scatter_in_cm != 0;
-    const int nsd = std::max(rx.n_edist, 1);
-    for (int k = 0; k < nsd; ++k) {
+    RxnState st;
+    st.has_angle_dist = rx.has_angle_dist != 0;
+    st.in_cm = rx.scatter_in_cm != 0;
+    const size_t first = sds->size();
+    for (int k = 0; k < std::max(rx.n_edist, 1); ++k) {
       const ndpp_ace_edist* ed = (rx.n_edist > 0) ? &rx.edist[k] : nullptr;
-      ndpp_ace_reaction a;
-      memset(&a, 0, sizeof(a));
-      a.MT = rx.MT;
-      a.law = ed ? ed->law : 0;
-      a.threshold_energy = nuc->energy[rx.threshold - 1];
-      if (st[ir].has_angle_dist) {
-        a.has_angle_dist = 1;
-        if (st[ir].fabricated) {   // the isotropic adist an earlier init wrote into rxn%adist
-          a.n_adist = 2; a.adist_energy = st[ir].fab_energy; a.adist_type = kIso;
-          a.adist_location = kZero; a.n_adist_data = 2; a.adist_data = kZeroD;
-        } else {
-          a.n_adist = rx.n_adist; a.adist_energy = rx.adist_energy; a.adist_type = rx.adist_type;
-          a.adist_location = rx.adist_location; a.n_adist_data = rx.n_adist_data;
-          a.adist_data = rx.adist_data;
-        }
-      }
-      if (ed) { a.n_edata = ed->n_data; a.edata = ed->data; }
+      const ndpp_ace_reaction a = reaction_view(nuc, rx, ed, st);
       int is_init = 0, law = 0, NE = 0, tot = 0;
-      rc = ndpp_scattdata_shape(&a, &is_init, &law, &NE, &tot);
+      int rc = ndpp_scattdata_shape(&a, &is_init, &law, &NE, &tot);
       if (rc) return rc;
       SD sd;
       sd.rxn = &rx;
       sd.is_init = is_init != 0;
       if (sd.is_init) {
-        // what init leaves behind (:135-223)
-        const bool had_adist = st[ir].has_angle_dist;
-        if (had_adist) {
-          sd.has_adist = true;
-          sd.has_edist = ed && ed->law != 3;
-        } else if (ed) {
-          if (ed->law == 4 || ed->law == 3 || ed->law == 9) {
-            sd.has_adist = true;
-            sd.has_edist = (ed->law == 9 || ed->law == 4);
-          } else {
-            sd.has_edist = true;
-          }
-        } else {
-          sd.has_adist = true;
-          st[ir].in_cm = true;   // :218
-        }
-        if (!had_adist && sd.has_adist) {      // rxn%adist now holds the isotropic table
-          st[ir].has_angle_dist = true;
-          st[ir].fabricated = true;
-          st[ir].fab_energy[1] = Etop;
-          st[ir].fab_energy[0] = (a.threshold_energy > e_bins[0]) ? a.threshold_energy : e_bins[0];
-        }
         sd.law = law;
-        sd.edist = sd.has_edist ? ed : nullptr;
-        sd.NE = NE;
-        sd.e_grid.resize(NE); sd.row_ptr.resize(NE + 1); sd.intt.resize(NE);
-        sd.eout.resize(tot); sd.pdf.resize(tot); sd.cdf.resize(tot);
-        // integrate_distro's dispatch below: angular-only tables (kind 1) go into host-side batches,
-        // law 9 reads column 1 of every row on the host; the rest is file 6
-        const bool file6_only = !(sd.has_adist && !sd.has_edist) && !(sd.has_adist && sd.law == 9);
-        const char* nk = getenv("NDPP_HIP_NO_DEVICE_TABLES");        // test hook: every table through the host
-        if (file6_only && !(nk && nk[0] == '1')) {
-          double* fd = nullptr;
-          rc = convert_distro_keep(M, &a, G, e_bins, NE, tot, sd.e_grid.data(), sd.row_ptr.data(),
-                                   sd.eout.data(), sd.pdf.data(), sd.cdf.data(), sd.intt.data(), &fd);
-          sd.f_dev = std::shared_ptr<double>(fd, [](double* q) { free_converted(q); });
-        } else {
-          sd.f.resize((size_t)tot * M);
-          rc = ndpp_convert_distro(M, &a, G, e_bins, NE, tot, sd.e_grid.data(), sd.row_ptr.data(),
-                                   sd.eout.data(), sd.pdf.data(), sd.cdf.data(), sd.intt.data(),
-                                   sd.f.data());
-        }
+        after_init(c, ed, a.threshold_energy, &sd, &st);
+        rc = convert_table(c, a, NE, tot, &sd);
         if (rc) return rc;
       }
-      sds.push_back(std::move(sd));
+      sds->push_back(std::move(sd));
     }
+    // scatter_in_cm as the integrators will see it (the flag lives on the reaction)
+    for (size_t k = first; k < sds->size(); ++k) (*sds)[k].in_cm = st.in_cm;
   }
-  // scatter_in_cm as the integrators will see it (the flag lives on the reaction)
-  {
-    size_t k = 0;
-    for (int ir = 0; ir < nuc->n_reaction; ++ir)
-      for (int j = 0; j < std::max(nuc->reactions[ir].n_edist, 1); ++j) sds[k++].in_cm = st[ir].in_cm;
-  }
+  return NDPP_OK;
+}
 
-  // ---- free-gas cutoff and inelastic threshold (:103-123)
-  double cutoff = 0.0, inel_thresh = Etop;
+// ---- free-gas cutoff and inelastic threshold (:103-123)
+int cutoff_and_threshold(const Call& c, const std::vector<SD>& sds, double* cutoff, double* inel_thresh) {
+  *cutoff = 0.0;
+  *inel_thresh = c.Etop;
   bool any = false;
   for (const SD& sd : sds) {
     if (!sd.is_init) continue;
     any = true;
-    if (sd.rxn->MT == 2) cutoff = nuc->freegas_cutoff;
-    else if (nuc->energy[sd.rxn->threshold - 1] < inel_thresh)
-      inel_thresh = nuc->energy[sd.rxn->threshold - 1];
+    if (sd.rxn->MT == 2) *cutoff = c.nuc->freegas_cutoff;
+    else if (c.nuc->energy[sd.rxn->threshold - 1] < *inel_thresh)
+      *inel_thresh = c.nuc->energy[sd.rxn->threshold - 1];
   }
-  if (!any) return fail(NDPP_EINVAL, "no scattering reaction in this nuclide");
+  return any ? NDPP_OK : fail(NDPP_EINVAL, "no scattering reaction in this nuclide");
+}
 
-  // ---- incoming grids (:134-135), or the caller's
+// ---- incoming grids (:134-135), or the caller's, and the matrices.  What a failure leaves allocated
+// is freed by the caller's one exit.
+int make_grids(Call& c, const std::vector<SD>& sds, double cutoff, double inel_thresh, const GivenGrids* given,
+               int nuscatt, ndpp_scatt_result* out) {
+  const ndpp_ace_nuclide* nuc = c.nuc;
   std::vector<ndpp_sd_grid> gs(sds.size());
   for (size_t k = 0; k < sds.size(); ++k) {
     gs[k].is_init = sds[k].is_init;
@@ -375,264 +415,377 @@ static int scatt_nuclide_impl(const ndpp_params* p, const ndpp_ace_nuclide* nuc,
     n_el = given->n_el;
     n_in = given->n_inel;
   } else {
-    rc = ndpp_create_ein_grid(p, (int)gs.size(), gs.data(), n_bins, e_bins, nuc->n_grid, nuc->energy,
-                              nuc->awr, nuc->kT, cutoff, inel_thresh, 0, nullptr, &n_el, 0, nullptr,
-                              &n_in);
+    const int rc = ndpp_create_ein_grid(c.p, (int)gs.size(), gs.data(), c.n_bins, c.e_bins, nuc->n_grid, nuc->energy,
+                                        nuc->awr, nuc->kT, cutoff, inel_thresh, 0, nullptr, &n_el, 0, nullptr, &n_in);
     if (rc) return rc;
   }
-  out->L = L; out->G = G; out->n_el = n_el; out->n_inel = n_in;
-  const size_t GL = (size_t)G * L;
-  hc.lap(0);
+  out->L = c.L; out->G = c.G; out->n_el = n_el; out->n_inel = n_in;
+  c.hc.lap(0);
   // (an empty given list still gets its one-element arrays: a NULL here means out of memory)
   out->ein_el = (double*)calloc(std::max<size_t>((size_t)n_el, 1), sizeof(double));
-  out->el_mat = (double*)calloc(std::max<size_t>((size_t)n_el * GL, 1), sizeof(double));
+  out->el_mat = (double*)calloc(std::max<size_t>((size_t)n_el * c.GL, 1), sizeof(double));
   if (n_in) {
     out->ein_inel = (double*)calloc((size_t)n_in, sizeof(double));
     // (overwritten as a whole by the download of the device-side reaction sum)
-    out->inel_mat = (double*)malloc(std::max<size_t>((size_t)n_in * GL, 1) * sizeof(double));
-    if (nuscatt) out->nuinel_mat = (double*)malloc(std::max<size_t>((size_t)n_in * GL, 1) * sizeof(double));
+    out->inel_mat = (double*)malloc(std::max<size_t>((size_t)n_in * c.GL, 1) * sizeof(double));
+    if (nuscatt) out->nuinel_mat = (double*)malloc(std::max<size_t>((size_t)n_in * c.GL, 1) * sizeof(double));
   }
   if (!out->ein_el || !out->el_mat || (n_in && (!out->ein_inel || !out->inel_mat)) ||
-      (n_in && nuscatt && !out->nuinel_mat)) {
-    ndpp_free_scatt_result(out);
+      (n_in && nuscatt && !out->nuinel_mat))
     return fail(NDPP_ENOMEM, "out of host memory for the result matrices");
-  }
   if (given) {
     std::copy(given->ein_el, given->ein_el + n_el, out->ein_el);
     if (n_in) std::copy(given->ein_inel, given->ein_inel + n_in, out->ein_inel);
   } else {
-    rc = ndpp_create_ein_grid(p, (int)gs.size(), gs.data(), n_bins, e_bins, nuc->n_grid, nuc->energy,
-                              nuc->awr, nuc->kT, cutoff, inel_thresh, n_el, out->ein_el, &n_el,
-                              std::max(n_in, 0), out->ein_inel, &n_in);
-    if (rc) { ndpp_free_scatt_result(out); return rc; }
+    const int rc = ndpp_create_ein_grid(c.p, (int)gs.size(), gs.data(), c.n_bins, c.e_bins, nuc->n_grid, nuc->energy,
+                                        nuc->awr, nuc->kT, cutoff, inel_thresh, n_el, out->ein_el, &n_el,
+                                        std::max(n_in, 0), out->ein_inel, &n_in);
+    if (rc) return rc;
   }
+  c.hc.lap(1);
+  return NDPP_OK;
+}
 
-  hc.lap(1);
-  // ---- the two grids
-  for (int pass = 0; pass < 2; ++pass) {
-    const bool elastic = pass == 0;
-    const int NEin = elastic ? n_el : n_in;
-    const double* Ein = elastic ? out->ein_el : out->ein_inel;
-    double* mat = elastic ? out->el_mat : out->inel_mat;
-    double* numat = elastic ? nullptr : out->nuinel_mat;
-    if (NEin == 0) continue;
-    std::vector<double> ein_b(NEin), w_hi(NEin), scale(NEin), pv(NEin), yield_(NEin);
-    ResultStage stage;
-    std::vector<int> row_lo(NEin), where_(NEin), status(NEin);
-    // The reaction sum of a large inelastic grid stays on the device; a small one (the shipped
-    // two-group structure: a few hundred KB) is summed here, which costs less than the
-    // allocations of the device matrices (0.4 s over the 423 nuclides of the library workload).
-    size_t dev_sum_min = (size_t)1 << 20;
-    if (const char* e = getenv("NDPP_HIP_DEV_SUM_MIN")) dev_sum_min = (size_t)atoll(e);   // test hook
-    const bool dev_sum = !elastic && (size_t)NEin * GL >= dev_sum_min;
-    ReactionSum rsum;
-    if (dev_sum) {
-      rc = rsum.init((size_t)NEin, GL, numat != nullptr, NEin);
-      if (rc) { ndpp_free_scatt_result(out); return rc; }
-    } else if (!elastic) {
-      std::fill(mat, mat + (size_t)NEin * GL, 0.0);
-      if (numat) std::fill(numat, numat + (size_t)NEin * GL, 0.0);
+// ---- one reaction on one grid: the incoming energies it contributes to (where: their rows of the
+// matrices), and per energy what the batch call (ein, row_lo, w_hi) and the sum (scale = sigma, pv =
+// p_valid, yield) need.  Sized for the grid once, refilled per reaction.
+struct Selection {
+  std::vector<int> where, row_lo;
+  std::vector<double> ein, w_hi, scale, pv, yield;
+  int nb = 0;
+  explicit Selection(int n) : where(n), row_lo(n), ein(n), w_hi(n), scale(n), pv(n), yield(n) {}
+};
+
+// scatt_interp_distro's bookkeeping; no device work
+int select_energies(const Call& c, const SD& sd, bool elastic, int NEin, const double* Ein, Selection* s) {
+  const ndpp_ace_nuclide* nuc = c.nuc;
+  const ndpp_ace_rxn& rx = *sd.rxn;
+  const double* sig = elastic ? nuc->elastic : rx.sigma;
+  const int nsig = elastic ? nuc->n_grid : rx.n_sigma;
+  if (!sig || nsig < 1) return fail(NDPP_EINVAL, "MT %d has no cross section", rx.MT);
+  if (sd.NE < 2) return fail(NDPP_EINVAL, "MT %d: fewer than 2 tabulated energies", rx.MT);
+  int nb = 0;
+  for (int iE = 0; iE < NEin; ++iE) {
+    const double E = Ein[iE];
+    // (E > Etop: the top point, copied by copy_top_rows)
+    if ((E <= nuc->energy[rx.threshold - 1] && rx.threshold > 1) || E > c.Etop) continue;  // :423-431
+    double sigS;
+    int iEg;
+    if (E >= nuc->energy[nuc->n_grid - 1]) {                             // :432-442
+      sigS = sig[nsig - 1];
+      iEg = sd.NE - 1;
+    } else {
+      int ni = (E <= nuc->energy[0]) ? 1 : bsearch1_clamped(nuc->energy, nuc->n_grid, E);
+      if (nuc->energy[ni - 1] == nuc->energy[ni]) ni = ni + 1;
+      const double fr = (E - nuc->energy[ni - 1]) / (nuc->energy[ni] - nuc->energy[ni - 1]);
+      ni = ni - rx.threshold + 1;
+      if (ni < 1 || ni + 1 > nsig) return fail(NDPP_EINVAL, "MT %d: cross section shorter than the grid", rx.MT);
+      sigS = (1.0 - fr) * sig[ni - 1] + fr * sig[ni];
+      if (sigS <= 0.0) continue;                                         // :466-468
+      iEg = (E < sd.e_grid[0]) ? 1 : ((E > sd.e_grid[sd.NE - 1]) ? -1 : bsearch1_clamped(sd.e_grid.data(), sd.NE, E));
+      if (iEg < 0) return fail(NDPP_EINVAL, "MT %d: E_in %g above its tabulated energies", rx.MT, E);
+      if (iEg + 1 <= sd.NE - 1 && sd.e_grid[iEg - 1] >= sd.e_grid[iEg]) iEg = iEg + 1;   // :480-482
     }
-    // Host-summed inelastic grid (few groups): the level reactions -- angular distribution only,
-    // dozens per nuclide, a few hundred incoming energies each -- are collected and integrated by
-    // ONE ndpp_elastic_leg_multi call (a "nuclide" of that call = one level: its Q and its rows)
-    // instead of one batch call each; every reaction's moments are kept until all are there and
-    // then summed in the reaction order of the loop, as before: same bits.
-    // NDPP_HIP_NO_LEVEL_BATCH=1 (test hook): one call per level.
-    struct Pending {
-      int nb = 0;
-      long off = -1;                          // >= 0: first row of this reaction in the level batch
-      std::vector<int> where;
-      std::vector<double> scale, pv, yld, res;
-    };
-    std::vector<Pending> pend;
-    ElasticDefer lvl;
-    const char* nlb = getenv("NDPP_HIP_NO_LEVEL_BATCH");
-    const bool host_sum = !elastic && !dev_sum;
-    const bool level_batch = host_sum && n_tab == 0 && !(nlb && nlb[0] == '1');
-    for (const SD& sd : sds) {
-      if (!sd.is_init) continue;
-      if ((sd.rxn->MT == 2) != elastic) continue;
-      const ndpp_ace_rxn& rx = *sd.rxn;
-      const double* sig = elastic ? nuc->elastic : rx.sigma;
-      const int nsig = elastic ? nuc->n_grid : rx.n_sigma;
-      if (!sig || nsig < 1) { ndpp_free_scatt_result(out); return fail(NDPP_EINVAL, "MT %d has no cross section", rx.MT); }
-      if (sd.NE < 2) { ndpp_free_scatt_result(out); return fail(NDPP_EINVAL, "MT %d: fewer than 2 tabulated energies", rx.MT); }
-      int nb = 0;
-      for (int iE = 0; iE < NEin; ++iE) {
-        const double E = Ein[iE];
-        if (E > Etop) continue;                                              // top point, copied below
-        if ((E <= nuc->energy[rx.threshold - 1] && rx.threshold > 1) || E > Etop) continue;  // :423-431
-        double sigS;
-        int iEg;
-        if (E >= nuc->energy[nuc->n_grid - 1]) {                             // :432-442
-          sigS = sig[nsig - 1];
-          iEg = sd.NE - 1;
-        } else {
-          int ni = (E <= nuc->energy[0]) ? 1 : bsearch1_clamped(nuc->energy, nuc->n_grid, E);
-          if (nuc->energy[ni - 1] == nuc->energy[ni]) ni = ni + 1;
-          const double fr = (E - nuc->energy[ni - 1]) / (nuc->energy[ni] - nuc->energy[ni - 1]);
-          ni = ni - rx.threshold + 1;
-          if (ni < 1 || ni + 1 > nsig) { ndpp_free_scatt_result(out); return fail(NDPP_EINVAL, "MT %d: cross section shorter than the grid", rx.MT); }
-          sigS = (1.0 - fr) * sig[ni - 1] + fr * sig[ni];
-          if (sigS <= 0.0) continue;                                         // :466-468
-          iEg = (E < sd.e_grid[0]) ? 1 : ((E > sd.e_grid[sd.NE - 1]) ? -1 : bsearch1_clamped(sd.e_grid.data(), sd.NE, E));
-          if (iEg < 0) { ndpp_free_scatt_result(out); return fail(NDPP_EINVAL, "MT %d: E_in %g above its tabulated energies", rx.MT, E); }
-          if (iEg + 1 <= sd.NE - 1 && sd.e_grid[iEg - 1] >= sd.e_grid[iEg]) iEg = iEg + 1;   // :480-482
-        }
-        double pval = 1.0;
-        if (sd.has_edist && sd.edist) {
-          rc = tab1(sd.edist->pv_n_regions, sd.edist->pv_nbt, sd.edist->pv_int, sd.edist->pv_n_pairs,
-                    sd.edist->pv_x, sd.edist->pv_y, E, &pval);
-          if (rc) { ndpp_free_scatt_result(out); return rc; }
-        }
-        where_[nb] = iE;
-        ein_b[nb] = E;
-        row_lo[nb] = iEg - 1;
-        w_hi[nb] = (E - sd.e_grid[iEg - 1]) / (sd.e_grid[iEg] - sd.e_grid[iEg - 1]);   // :542
-        scale[nb] = sigS;
-        pv[nb] = pval;
-        ++nb;
-      }
-      hc.lap(2);
-      if (nb == 0) continue;
-      // integrate_distro's dispatch (:533-656)
-      int kind;
-      if (sd.has_adist && !sd.has_edist) kind = 1;
-      else if (sd.in_cm) kind = 2;
-      else if (sd.has_adist && sd.law == 9) kind = 3;
-      else kind = 4;
-      if (kind == 1 && elastic && defer) {
-        const int k = (int)defer->A.size();
-        defer->A.push_back(nuc->awr); defer->kT.push_back(nuc->kT);
-        defer->cut.push_back(nuc->freegas_cutoff); defer->Q.push_back(rx.Q_value);
-        for (int j = 0; j < nb; ++j) {
-          defer->ein.push_back(ein_b[j]); defer->w.push_back(w_hi[j]);
-          defer->nuc.push_back(k); defer->row.push_back(defer->n_rows + row_lo[j]);
-          defer->dst.push_back(mat + (size_t)where_[j] * GL);
-        }
-        defer->f_tab.insert(defer->f_tab.end(), sd.f.begin(), sd.f.end());
-        defer->n_rows += sd.NE;
-        continue;
-      }
-      double* res = nullptr;
-      DeviceSink* sink = nullptr;
-      const bool deferred = level_batch && kind == 1;
-      if (host_sum) {
-        pend.emplace_back();
-        Pending& pd = pend.back();
-        pd.nb = nb;
-        pd.where.assign(where_.begin(), where_.begin() + nb);
-        pd.scale.assign(scale.begin(), scale.begin() + nb);
-        pd.pv.assign(pv.begin(), pv.begin() + nb);
-        if (!deferred) { pd.res.resize((size_t)nb * GL); res = pd.res.data(); }
-      } else if (!dev_sum) {
-        res = stage.get((size_t)nb * GL);
-        if (!res) { ndpp_free_scatt_result(out); return fail(NDPP_ENOMEM, "out of host memory for a reaction's moments"); }
-      }
-      if (!elastic) {
-        for (int k = 0; k < nb; ++k) {
-          yield_[k] = (double)rx.multiplicity;
-          if (numat && rx.has_mult_E) {
-            rc = tab1(rx.mE_n_regions, rx.mE_nbt, rx.mE_int, rx.mE_n_pairs, rx.mE_x, rx.mE_y, ein_b[k], &yield_[k]);
-            if (rc) { ndpp_free_scatt_result(out); return rc; }
-          }
-        }
-      }
-      if (dev_sum) {
-        rc = rsum.stage(nb, where_.data(), scale.data(), pv.data(), yield_.data());
-        if (rc) { ndpp_free_scatt_result(out); return rc; }
-        sink = &rsum;
-      }
-      if (host_sum) pend.back().yld.assign(yield_.begin(), yield_.begin() + nb);
-      if (deferred) {
-        const int k = (int)lvl.A.size();
-        pend.back().off = (long)lvl.ein.size();
-        lvl.A.push_back(nuc->awr); lvl.kT.push_back(nuc->kT); lvl.cut.push_back(0.0); lvl.Q.push_back(rx.Q_value);
-        for (int j = 0; j < nb; ++j) {
-          lvl.ein.push_back(ein_b[j]); lvl.w.push_back(w_hi[j]);
-          lvl.nuc.push_back(k); lvl.row.push_back(lvl.n_rows + row_lo[j]);
-        }
-        lvl.f_tab.insert(lvl.f_tab.end(), sd.f.begin(), sd.f.end());
-        lvl.n_rows += sd.NE;
-        hc.lap(2);
-        continue;
-      }
-      if (kind == 1 && n_tab > 0) {
-        rc = elastic_tab_batch_sink(p, nuc->awr, nuc->kT, elastic ? nuc->freegas_cutoff : 0.0, rx.Q_value, nb,
-                                    ein_b.data(), row_lo.data(), w_hi.data(), sd.NE, sd.f.data(), G, e_bins, n_tab,
-                                    res, status.data(), sink);
-      } else if (kind == 1) {
-        rc = elastic_leg_batch_sink(p, nuc->awr, nuc->kT, elastic ? nuc->freegas_cutoff : 0.0,
-                                    rx.Q_value, nb, ein_b.data(), row_lo.data(), w_hi.data(), sd.NE,
-                                    sd.f.data(), G, e_bins, res, status.data(), sink);
-      } else if (kind == 3) {
-        std::vector<double> ftab((size_t)sd.NE * M);   // column 1 of every row
-        for (int k = 0; k < sd.NE; ++k)
-          std::copy(sd.f.begin() + (size_t)sd.row_ptr[k] * M, sd.f.begin() + (size_t)(sd.row_ptr[k] + 1) * M,
-                    ftab.begin() + (size_t)k * M);
-        rc = n_tab > 0 ? law9_tab_batch_sink(p, nb, ein_b.data(), row_lo.data(), w_hi.data(), sd.NE, ftab.data(),
-                                             sd.edist->n_data, sd.edist->data, G, e_bins, n_tab, res,
-                                             status.data(), sink)
-                       : law9_leg_batch_sink(p, nb, ein_b.data(), row_lo.data(), w_hi.data(), sd.NE, ftab.data(),
-                                             sd.edist->n_data, sd.edist->data, G, e_bins, res, status.data(), sink);
-      } else {
-        rc = file6_batch_sink(p, nuc->awr, kind == 2 ? 1 : 0, nb, ein_b.data(), row_lo.data(), sd.NE,
-                              sd.e_grid.data(), sd.row_ptr.data(), sd.eout.data(), sd.pdf.data(),
-                              sd.intt.data(), sd.f.data(), G, e_bins, n_tab, res, status.data(), sink,
-                              sd.f_dev.get());
-      }
-      hc.lap(3);
-      if (rc) { ndpp_free_scatt_result(out); return rc; }
-      if (elastic)                                            // assigned, not scaled (:494-497, scatt.F90:660)
-        parallel_rows(nb, GL * 2 * sizeof(double), [&](int k0, int k1) {
-          for (int k = k0; k < k1; ++k)
-            std::copy(res + (size_t)k * GL, res + (size_t)(k + 1) * GL, mat + (size_t)where_[k] * GL);
-        });
-      hc.lap(4);
+    double pval = 1.0;
+    if (sd.has_edist && sd.edist) {
+      const int rc = tab1(sd.edist->pv_n_regions, sd.edist->pv_nbt, sd.edist->pv_int, sd.edist->pv_n_pairs,
+                          sd.edist->pv_x, sd.edist->pv_y, E, &pval);
+      if (rc) return rc;
     }
-    if (host_sum) {
-      std::vector<double> lvl_res;
-      if (!lvl.ein.empty()) {
-        const int n = (int)lvl.ein.size();
-        lvl_res.resize((size_t)n * GL);
-        std::vector<int> lst(n);
-        rc = ndpp_elastic_leg_multi(p, (int)lvl.A.size(), lvl.A.data(), lvl.kT.data(), lvl.cut.data(), lvl.Q.data(),
-                                    n, lvl.ein.data(), lvl.nuc.data(), lvl.row.data(), lvl.w.data(), lvl.n_rows,
-                                    lvl.f_tab.data(), G, e_bins, lvl_res.data(), lst.data(), nullptr);
-        hc.lap(3);
-        if (rc) { ndpp_free_scatt_result(out); return rc; }
-      }
-      for (const Pending& pd : pend)             // the reaction sum, in the order of the loop above
-        for (int k = 0; k < pd.nb; ++k) {
-          double* dst = mat + (size_t)pd.where[k] * GL;
-          double* nudst = numat ? numat + (size_t)pd.where[k] * GL : nullptr;
-          const double* src = pd.off >= 0 ? lvl_res.data() + (size_t)(pd.off + k) * GL : pd.res.data() + (size_t)k * GL;
-          for (size_t j = 0; j < GL; ++j) {
-            const double t = src[j] * pd.scale[k] * pd.pv[k];     // :496
-            dst[j] = dst[j] + t;                                  // scatt.F90:753
-            if (nudst) nudst[j] = nudst[j] + pd.yld[k] * t;       // :762
-          }
-        }
-      hc.lap(4);
+    s->where[nb] = iE;
+    s->ein[nb] = E;
+    s->row_lo[nb] = iEg - 1;
+    s->w_hi[nb] = (E - sd.e_grid[iEg - 1]) / (sd.e_grid[iEg] - sd.e_grid[iEg - 1]);   // :542
+    s->scale[nb] = sigS;
+    s->pv[nb] = pval;
+    ++nb;
+  }
+  s->nb = nb;
+  return NDPP_OK;
+}
+
+// the nu-scatter yields of the selected energies (scatt.F90:745-762); the table only where it is summed
+int select_yields(const ndpp_ace_rxn& rx, bool with_nu, Selection* s) {
+  for (int k = 0; k < s->nb; ++k) {
+    s->yield[k] = (double)rx.multiplicity;
+    if (with_nu && rx.has_mult_E) {
+      const int rc = tab1(rx.mE_n_regions, rx.mE_nbt, rx.mE_int, rx.mE_n_pairs, rx.mE_x, rx.mE_y, s->ein[k],
+                          &s->yield[k]);
+      if (rc) return rc;
     }
-    if (dev_sum) {
-      rc = rsum.download(mat, numat);
-      if (rc) { ndpp_free_scatt_result(out); return rc; }
-      hc.lap(4);
-    }
-    if (elastic && defer) {                                  // filled and copied by the caller
-      defer->tops.push_back({mat, Ein, NEin});
-      continue;
-    }
-    for (int iE = 1; iE < NEin; ++iE)                        // scatt.F90:664-670, :766-774
-      if (Ein[iE] > Etop) {
-        std::copy(mat + (size_t)(iE - 1) * GL, mat + (size_t)iE * GL, mat + (size_t)iE * GL);
-        if (numat) std::copy(numat + (size_t)(iE - 1) * GL, numat + (size_t)iE * GL, numat + (size_t)iE * GL);
-      }
-    hc.lap(5);
   }
   return NDPP_OK;
+}
+
+// ---- integrate_distro for the selected energies of one reaction: the batch call of its kind, Legendre
+// or tabular, into the host array res [nb][GL] or (res null) the sink.  cutoff: the free-gas cutoff of
+// the elastic grid, 0 on the inelastic one.
+int integrate_reaction(const Call& c, const SD& sd, int kind, double cutoff, const Selection& s, double* res,
+                       DeviceSink* sink) {
+  const ndpp_ace_nuclide* nuc = c.nuc;
+  std::vector<int> status(s.nb);
+  if (kind == 1 && c.n_tab > 0)
+    return elastic_tab_batch_sink(c.p, nuc->awr, nuc->kT, cutoff, sd.rxn->Q_value, s.nb, s.ein.data(),
+                                  s.row_lo.data(), s.w_hi.data(), sd.NE, sd.f.data(), c.G, c.e_bins, c.n_tab, res,
+                                  status.data(), sink);
+  if (kind == 1)
+    return elastic_leg_batch_sink(c.p, nuc->awr, nuc->kT, cutoff, sd.rxn->Q_value, s.nb, s.ein.data(),
+                                  s.row_lo.data(), s.w_hi.data(), sd.NE, sd.f.data(), c.G, c.e_bins, res,
+                                  status.data(), sink);
+  if (kind == 3) {
+    std::vector<double> ftab((size_t)sd.NE * c.M);   // column 1 of every row
+    for (int k = 0; k < sd.NE; ++k)
+      std::copy(sd.f.begin() + (size_t)sd.row_ptr[k] * c.M, sd.f.begin() + (size_t)(sd.row_ptr[k] + 1) * c.M,
+                ftab.begin() + (size_t)k * c.M);
+    return c.n_tab > 0
+               ? law9_tab_batch_sink(c.p, s.nb, s.ein.data(), s.row_lo.data(), s.w_hi.data(), sd.NE, ftab.data(),
+                                     sd.edist->n_data, sd.edist->data, c.G, c.e_bins, c.n_tab, res, status.data(), sink)
+               : law9_leg_batch_sink(c.p, s.nb, s.ein.data(), s.row_lo.data(), s.w_hi.data(), sd.NE, ftab.data(),
+                                     sd.edist->n_data, sd.edist->data, c.G, c.e_bins, res, status.data(), sink);
+  }
+  return file6_batch_sink(c.p, nuc->awr, kind == 2 ? 1 : 0, s.nb, s.ein.data(), s.row_lo.data(), sd.NE,
+                          sd.e_grid.data(), sd.row_ptr.data(), sd.eout.data(), sd.pdf.data(), sd.intt.data(),
+                          sd.f.data(), c.G, c.e_bins, c.n_tab, res, status.data(), sink, sd.f_dev.get());
+}
+
+// ---- ElasticDefer: collect, run, and the top point
+
+// One angular-only reaction with its selected energies as the next "nuclide" of the multi call.  mat: the
+// matrix its (L,G) blocks go to (null: the caller keeps track).  Returns its first row in the call.
+size_t append_reaction(ElasticDefer* d, const ndpp_ace_nuclide* nuc, double cutoff, const SD& sd,
+                       const Selection& s, double* mat, size_t GL) {
+  const size_t first = d->ein.size();
+  const int k = (int)d->A.size();
+  d->A.push_back(nuc->awr); d->kT.push_back(nuc->kT); d->cut.push_back(cutoff); d->Q.push_back(sd.rxn->Q_value);
+  for (int j = 0; j < s.nb; ++j) {
+    d->ein.push_back(s.ein[j]); d->w.push_back(s.w_hi[j]);
+    d->nuc.push_back(k); d->row.push_back(d->n_rows + s.row_lo[j]);
+    if (mat) d->dst.push_back(mat + (size_t)s.where[j] * GL);
+  }
+  d->f_tab.insert(d->f_tab.end(), sd.f.begin(), sd.f.end());
+  d->n_rows += sd.NE;
+  return first;
+}
+
+// what was collected through ONE ndpp_elastic_leg_multi call: rows [d.ein.size()][G * p->order]
+int run_elastic_defer(const ndpp_params* p, const ElasticDefer& d, int G, const double* e_bins,
+                      std::vector<double>* rows) {
+  const int n = (int)d.ein.size();
+  if (n == 0) return NDPP_OK;
+  rows->resize((size_t)n * G * p->order);
+  std::vector<int> status(n);
+  return ndpp_elastic_leg_multi(p, (int)d.A.size(), d.A.data(), d.kT.data(), d.cut.data(), d.Q.data(), n,
+                                d.ein.data(), d.nuc.data(), d.row.data(), d.w.data(), d.n_rows, d.f_tab.data(), G,
+                                e_bins, rows->data(), status.data(), nullptr);
+}
+
+// an incoming energy above the top group edge takes the row before it (scatt.F90:664-670, :766-774)
+void copy_top_rows(int NEin, const double* Ein, double Etop, size_t GL, double* mat, double* numat) {
+  for (int iE = 1; iE < NEin; ++iE)
+    if (Ein[iE] > Etop) {
+      std::copy(mat + (size_t)(iE - 1) * GL, mat + (size_t)iE * GL, mat + (size_t)iE * GL);
+      if (numat) std::copy(numat + (size_t)(iE - 1) * GL, numat + (size_t)iE * GL, numat + (size_t)iE * GL);
+    }
+}
+
+// ---- The three ways a reaction's moments reach the matrices of a grid: take() one reaction with its
+// selected energies, finish() after the last.
+
+// The elastic grid: assigned row by row, not scaled (:494-497, scatt.F90:660).  In a library call the
+// angular-only reaction is collected into the mixed batch instead, which fills its rows.
+struct ElasticAssign {
+  double* mat;
+  ElasticDefer* defer;
+  ResultStage stage;
+  int take(Call& c, const SD& sd, int kind, const Selection& s) {
+    if (kind == 1 && defer) {
+      append_reaction(defer, c.nuc, c.nuc->freegas_cutoff, sd, s, mat, c.GL);
+      return NDPP_OK;
+    }
+    double* res = stage.get((size_t)s.nb * c.GL);
+    if (!res) return fail(NDPP_ENOMEM, "out of host memory for a reaction's moments");
+    const int rc = integrate_reaction(c, sd, kind, c.nuc->freegas_cutoff, s, res, nullptr);
+    c.hc.lap(3);
+    if (rc) return rc;
+    parallel_rows(s.nb, c.GL * 2 * sizeof(double), [&](int k0, int k1) {
+      for (int k = k0; k < k1; ++k)
+        std::copy(res + (size_t)k * c.GL, res + (size_t)(k + 1) * c.GL, mat + (size_t)s.where[k] * c.GL);
+    });
+    c.hc.lap(4);
+    return NDPP_OK;
+  }
+  int finish(Call&) { return NDPP_OK; }
+};
+
+// A small inelastic grid, summed on the host.  The level reactions -- angular distribution only,
+// dozens per nuclide, a few hundred incoming energies each -- are collected and integrated by
+// ONE ndpp_elastic_leg_multi call (a "nuclide" of that call = one level: its Q and its rows)
+// instead of one batch call each; every reaction's moments are kept until all are there and
+// then summed in the reaction order of take(): same bits as one call per level
+// (Hooks::level_batch off; the tabular output has no multi call).
+struct HostSum {
+  struct Pending {
+    int nb = 0;
+    long off = -1;                          // >= 0: first row of this reaction in the level batch
+    std::vector<int> where;
+    std::vector<double> scale, pv, yld, res;
+  };
+  double *mat, *numat;
+  bool level_batch;
+  std::vector<Pending> pend;
+  ElasticDefer lvl;
+  HostSum(const Call& c, int NEin, double* m, double* nm)
+      : mat(m), numat(nm), level_batch(c.n_tab == 0 && c.hooks.level_batch) {
+    std::fill(mat, mat + (size_t)NEin * c.GL, 0.0);
+    if (numat) std::fill(numat, numat + (size_t)NEin * c.GL, 0.0);
+  }
+  int take(Call& c, const SD& sd, int kind, const Selection& s) {
+    pend.emplace_back();
+    Pending& pd = pend.back();
+    pd.nb = s.nb;
+    pd.where.assign(s.where.begin(), s.where.begin() + s.nb);
+    pd.scale.assign(s.scale.begin(), s.scale.begin() + s.nb);
+    pd.pv.assign(s.pv.begin(), s.pv.begin() + s.nb);
+    pd.yld.assign(s.yield.begin(), s.yield.begin() + s.nb);
+    if (level_batch && kind == 1) {
+      pd.off = (long)append_reaction(&lvl, c.nuc, 0.0, sd, s, nullptr, c.GL);
+      c.hc.lap(2);
+      return NDPP_OK;
+    }
+    pd.res.resize((size_t)s.nb * c.GL);
+    const int rc = integrate_reaction(c, sd, kind, 0.0, s, pd.res.data(), nullptr);
+    c.hc.lap(3);
+    return rc;
+  }
+  int finish(Call& c) {
+    std::vector<double> lvl_res;
+    const int rc = run_elastic_defer(c.p, lvl, c.G, c.e_bins, &lvl_res);
+    if (!lvl.ein.empty()) c.hc.lap(3);
+    if (rc) return rc;
+    for (const Pending& pd : pend)             // the reaction sum, in the order of take()
+      for (int k = 0; k < pd.nb; ++k) {
+        double* dst = mat + (size_t)pd.where[k] * c.GL;
+        double* nudst = numat ? numat + (size_t)pd.where[k] * c.GL : nullptr;
+        const double* src = pd.off >= 0 ? lvl_res.data() + (size_t)(pd.off + k) * c.GL : pd.res.data() + (size_t)k * c.GL;
+        for (size_t j = 0; j < c.GL; ++j) {
+          const double t = src[j] * pd.scale[k] * pd.pv[k];     // :496
+          dst[j] = dst[j] + t;                                  // scatt.F90:753
+          if (nudst) nudst[j] = nudst[j] + pd.yld[k] * t;       // :762
+        }
+      }
+    c.hc.lap(4);
+    return NDPP_OK;
+  }
+};
+
+// A large inelastic grid, summed on the device through ReactionSum: one staged upload per reaction, the
+// batch call hands its moments to the sink, one download at the end.
+struct DeviceSum {
+  double *mat, *numat;
+  ReactionSum rsum;
+  int init(const Call& c, int NEin) { return rsum.init((size_t)NEin, c.GL, numat != nullptr, NEin); }
+  int take(Call& c, const SD& sd, int kind, const Selection& s) {
+    int rc = rsum.stage(s.nb, s.where.data(), s.scale.data(), s.pv.data(), s.yield.data());
+    if (rc) return rc;
+    rc = integrate_reaction(c, sd, kind, 0.0, s, nullptr, &rsum);
+    c.hc.lap(3);
+    return rc;
+  }
+  int finish(Call& c) {
+    const int rc = rsum.download(mat, numat);
+    if (rc) return rc;
+    c.hc.lap(4);
+    return NDPP_OK;
+  }
+};
+
+// the reactions of one grid, in their order, through one of the three
+template <class Acc>
+int run_reactions(Call& c, const std::vector<SD>& sds, bool elastic, int NEin, const double* Ein, bool with_nu,
+                  Acc& acc) {
+  Selection s(NEin);
+  for (const SD& sd : sds) {
+    if (!sd.is_init || (sd.rxn->MT == 2) != elastic) continue;
+    int rc = select_energies(c, sd, elastic, NEin, Ein, &s);
+    if (rc) return rc;
+    c.hc.lap(2);
+    if (s.nb == 0) continue;
+    if (!elastic) rc = select_yields(*sd.rxn, with_nu, &s);
+    if (rc == NDPP_OK) rc = acc.take(c, sd, distro_kind(sd), s);
+    if (rc) return rc;
+  }
+  return acc.finish(c);
+}
+
+// ---- calc_elastic_grid / calc_inelastic_grid.  The reaction sum of a large inelastic grid stays on
+// the device; a small one (the shipped two-group structure: a few hundred KB) is summed on the host,
+// which costs less than the allocations of the device matrices (0.4 s over the 423 nuclides of the
+// library workload).  Hooks::dev_sum_min moves the border.
+int run_grid(Call& c, const std::vector<SD>& sds, bool elastic, ndpp_scatt_result* out, ElasticDefer* defer) {
+  const int NEin = elastic ? out->n_el : out->n_inel;
+  const double* Ein = elastic ? out->ein_el : out->ein_inel;
+  double* mat = elastic ? out->el_mat : out->inel_mat;
+  double* numat = elastic ? nullptr : out->nuinel_mat;
+  if (NEin == 0) return NDPP_OK;
+  int rc;
+  if (elastic) {
+    ElasticAssign acc{mat, defer};
+    rc = run_reactions(c, sds, true, NEin, Ein, false, acc);
+  } else if ((size_t)NEin * c.GL >= c.hooks.dev_sum_min) {
+    DeviceSum acc{mat, numat};
+    rc = acc.init(c, NEin);
+    if (rc == NDPP_OK) rc = run_reactions(c, sds, false, NEin, Ein, numat != nullptr, acc);
+  } else {
+    HostSum acc(c, NEin, mat, numat);
+    rc = run_reactions(c, sds, false, NEin, Ein, numat != nullptr, acc);
+  }
+  if (rc) return rc;
+  if (elastic && defer) {                                  // filled and copied by the caller
+    defer->tops.push_back({mat, Ein, NEin});
+    return NDPP_OK;
+  }
+  copy_top_rows(NEin, Ein, c.Etop, c.GL, mat, numat);
+  c.hc.lap(5);
+  return NDPP_OK;
+}
+
+}  // namespace
+}  // namespace ndpp
+
+using namespace ndpp;
+
+extern "C" void ndpp_free_scatt_result(ndpp_scatt_result* r) {
+  if (!r) return;
+  free(r->ein_el); free(r->ein_inel); free(r->el_mat); free(r->inel_mat); free(r->nuinel_mat);
+  memset(r, 0, sizeof(*r));
+}
+
+// n_tab = 0: Legendre moments (L = p->order); n_tab > 0: calc_scatt with scatt_type = tabular,
+// n_tab lab-cosine bins per group (the tabular batch calls; no deferred or level batches).
+// defer: a library's mixed elastic batch; given: the caller's grids instead of create_Ein_grid's.
+static int scatt_nuclide_impl(const ndpp_params* p, const ndpp_ace_nuclide* nuc, int n_bins,
+                              const double* e_bins, int nuscatt, ndpp_scatt_result* out,
+                              ElasticDefer* defer, int n_tab = 0, const GivenGrids* given = nullptr) {
+  if (!p || !nuc || !e_bins || !out) return fail(NDPP_EINVAL, "NULL argument");
+  memset(out, 0, sizeof(*out));
+  if (n_tab < 0 || n_tab > NDPP_MAX_TAB_BINS)
+    return fail(NDPP_EINVAL, "n_tab=%d outside 1..%d", n_tab, NDPP_MAX_TAB_BINS);
+  if (n_tab > 0 && defer)
+    return fail(NDPP_EINVAL, "tabular output has no deferred (mixed-nuclide) elastic batch");
+  if (n_bins < 2) return fail(NDPP_EINVAL, "need at least one group");
+  if (nuc->n_grid < 2 || !nuc->energy || !nuc->elastic)
+    return fail(NDPP_EINVAL, "nuclide energy grid / elastic cross section missing");
+  if (nuc->n_reaction < 1 || !nuc->reactions) return fail(NDPP_EINVAL, "nuclide has no reactions");
+  Call c(p, nuc, n_bins, e_bins, n_tab);
+  std::vector<SD> sds;
+  double cutoff, inel_thresh;
+  int rc = convert_reactions(c, &sds);
+  if (rc == NDPP_OK) rc = cutoff_and_threshold(c, sds, &cutoff, &inel_thresh);
+  if (rc == NDPP_OK) rc = make_grids(c, sds, cutoff, inel_thresh, given, nuscatt, out);
+  if (rc == NDPP_OK) rc = run_grid(c, sds, true, out, defer);
+  if (rc == NDPP_OK) rc = run_grid(c, sds, false, out, nullptr);
+  if (rc != NDPP_OK) ndpp_free_scatt_result(out);   // the one exit of every failure after the arguments
+  return rc;
 }
 
 extern "C" int ndpp_scatt_nuclide(const ndpp_params* p, const ndpp_ace_nuclide* nuc, int n_bins,
@@ -640,8 +793,28 @@ extern "C" int ndpp_scatt_nuclide(const ndpp_params* p, const ndpp_ace_nuclide* 
   return scatt_nuclide_impl(p, nuc, n_bins, e_bins, nuscatt, out, nullptr);
 }
 
-// calc_scatt for a list of nuclides, their elastic grids in ONE mixed batch.  grids: null (every
-// nuclide builds its own, ndpp_scatt_library) or one GivenGrids per nuclide (ndpp_scatt_library_at).
+// the deferred elastic grids of a library as ONE mixed batch, each row to its matrix; then the top points
+static int flush_library(const ndpp_params* p, int n_bins, const double* e_bins, ElasticDefer* d) {
+  int rc = NDPP_OK;
+  if (!d->ein.empty()) {
+    const int G = n_bins - 1;
+    const size_t GL = (size_t)G * p->order;
+    std::vector<double> res;
+    rc = run_elastic_defer(p, *d, G, e_bins, &res);
+    if (rc == NDPP_OK) {
+      for (size_t i = 0; i < d->dst.size(); ++i)
+        std::copy(res.begin() + i * GL, res.begin() + (i + 1) * GL, d->dst[i]);
+      for (const ElasticDefer::Top& t : d->tops) copy_top_rows(t.n, t.Ein, e_bins[G], GL, t.mat, nullptr);
+    }
+    *d = ElasticDefer();
+  }
+  return rc;
+}
+
+// calc_scatt for a list of nuclides, their elastic grids in ONE mixed batch -- or several, when the
+// tables collected so far approach what one batch call addresses (32-bit byte offsets into f_tab:
+// run_batch_d).  grids: null (every nuclide builds its own, ndpp_scatt_library) or one GivenGrids per
+// nuclide (ndpp_scatt_library_at).
 static int scatt_library_impl(const ndpp_params* p, int n_nuclides, const ndpp_ace_nuclide* nuclides,
                               int n_bins, const double* e_bins, int nuscatt, const GivenGrids* grids,
                               ndpp_scatt_result* out) {
@@ -650,35 +823,12 @@ static int scatt_library_impl(const ndpp_params* p, int n_nuclides, const ndpp_a
   for (int k = 0; k < n_nuclides; ++k) memset(&out[k], 0, sizeof(out[k]));
   ElasticDefer d;
   int rc = NDPP_OK;
-  // the deferred elastic grids as ONE mixed batch -- or several, when the tables collected so far
-  // approach what one batch call addresses (32-bit byte offsets into f_tab: run_batch_d)
-  auto flush = [&]() -> int {
-    if (d.ein.empty()) return NDPP_OK;
-    const int G = n_bins - 1, n = (int)d.ein.size();
-    const size_t GL = (size_t)G * p->order;
-    std::vector<double> res((size_t)n * GL);
-    std::vector<int> status(n);
-    int rc = ndpp_elastic_leg_multi(p, (int)d.A.size(), d.A.data(), d.kT.data(), d.cut.data(),
-                                    d.Q.data(), n, d.ein.data(), d.nuc.data(), d.row.data(),
-                                    d.w.data(), d.n_rows, d.f_tab.data(), G, e_bins, res.data(),
-                                    status.data(), nullptr);
-    if (rc == NDPP_OK) {
-      for (int i = 0; i < n; ++i) std::copy(res.begin() + (size_t)i * GL, res.begin() + (size_t)(i + 1) * GL, d.dst[i]);
-      const double Etop = e_bins[G];
-      for (const ElasticDefer::Top& t : d.tops)                // scatt.F90:664-670
-        for (int iE = 1; iE < t.n; ++iE)
-          if (t.Ein[iE] > Etop)
-            std::copy(t.mat + (size_t)(iE - 1) * GL, t.mat + (size_t)iE * GL, t.mat + (size_t)iE * GL);
-    }
-    d = ElasticDefer();
-    return rc;
-  };
   constexpr size_t kFlushBytes = (size_t)3 << 30;
   for (int k = 0; k < n_nuclides && rc == NDPP_OK; ++k) {
     rc = scatt_nuclide_impl(p, &nuclides[k], n_bins, e_bins, nuscatt, &out[k], &d, 0, grids ? &grids[k] : nullptr);
-    if (rc == NDPP_OK && d.f_tab.size() * sizeof(double) > kFlushBytes) rc = flush();
+    if (rc == NDPP_OK && d.f_tab.size() * sizeof(double) > kFlushBytes) rc = flush_library(p, n_bins, e_bins, &d);
   }
-  if (rc == NDPP_OK) rc = flush();
+  if (rc == NDPP_OK) rc = flush_library(p, n_bins, e_bins, &d);
   if (rc != NDPP_OK)
     for (int k = 0; k < n_nuclides; ++k) ndpp_free_scatt_result(&out[k]);
   return rc;
