@@ -679,6 +679,42 @@ int ndpp_grid_error(int L, int G, int n, const double *x, const double *y /* [n]
                     const double *x_mid /* [n-1] */, const double *y_mid /* [n-1][G][L] */,
                     double *err /* [n-1] */, int *arg /* [n-1] */);
 
+/* ---- error-bounded thinning of an incoming-energy grid.  Replaces nothing:
+ * thin_grid (above) tests a point against the last kept point and its right neighbour only, under
+ * an element-wise relative metric, so its tolerance bounds nothing.  Here every candidate segment is
+ * measured.  x[n] strictly increasing, positive and finite; rows y[n][G][L] and, on the same grid,
+ * y2[n][G][L] or NULL (inelastic with nu-inelastic riding along).  With
+ *   lx[i] = log(x[i])                    (the host's log, once per point)
+ *   s[i]  = max over g of |y[i][g][0]|   (s2 alike for y2)
+ * and, for a < k < b,
+ *   f          = (lx[k] - lx[a]) / (lx[b] - lx[a])
+ *   d(a,k,b)   = max over elements e of | y[a][e] + (y[b][e] - y[a][e]) * f - y[k][e] |
+ *   err(a,k,b) = d / max(s[a], s[k], s[b])    (0 when that scale is 0; +inf when an element
+ *                involved, or the value they produce, is a NaN or an infinity; with y2 the larger
+ *                of the two sections' values, each over its own scale)
+ * the result is, for d = 2..window,
+ *   seg_err[a][d-2] = max over a < k < a+d of err(a, k, a+d)
+ *                     -1 when a + d > n - 1; +inf when some k strictly inside is a must-keep point
+ *                     (x[k] equal to one of tokeep[n_keep]).
+ * Only + - * / fabs and comparisons run on the device, in the order written, without contraction: a
+ * host restatement reproduces seg_err bit for bit (ndpp_amd/thin.py: segment_errors_numpy).
+ * NDPP_EINVAL, decided before the device is touched: L or G < 1, n < 2, window outside 2..64, a NULL
+ * pointer (tokeep may be NULL when n_keep is 0), n_keep < 0, x not strictly increasing, positive and
+ * finite, sizes whose bytes overflow.  Without a device NDPP_EDEVICE.                              */
+int ndpp_thin_segments(int L, int G, int n, const double *x, const double *y /* [n][G][L] */,
+                       const double *y2 /* [n][G][L] or NULL */, int n_keep, const double *tokeep,
+                       int window, double *seg_err /* [n][window-1] */);
+/* ndpp_thin_segments plus the chain over it.  A segment (a, a+d) is admissible when
+ * 0 <= seg_err[a][d-2] <= tol; (a, a+1) always is.  reach[a] is the largest admissible a+d within
+ * the window; the kept points are 0 -> reach[0] -> reach[reach[0]] -> ... -> n-1.  kept[0..*n_kept)
+ * receives their indices in increasing order (no data moves: the caller gathers rows by them) and
+ * *max_err the largest seg_err along the chain: every dropped point is within it, and so within tol,
+ * of the interpolation between its two kept neighbours.  Also NDPP_EINVAL: tol not finite or < 0.
+ * n = 2: both points kept, *max_err = 0.                                                          */
+int ndpp_thin_bounded(int L, int G, int n, const double *x, const double *y, const double *y2,
+                      int n_keep, const double *tokeep, double tol, int window,
+                      int *kept /* [n] */, int *n_kept, double *max_err);
+
 #ifdef __cplusplus
 }
 #endif

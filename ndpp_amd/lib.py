@@ -46,6 +46,7 @@ EXPORTS = [
     "ndpp_scatt_positivity", "ndpp_expand_moments",
     "ndpp_elastic_tab_batch", "ndpp_file6_tab_batch", "ndpp_law9_tab_batch", "ndpp_scatt_nuclide_tab",
     "ndpp_scatt_library_tab", "ndpp_scatt_library_at", "ndpp_grid_error",
+    "ndpp_thin_segments", "ndpp_thin_bounded",
 ]
 
 
@@ -586,6 +587,10 @@ def load(build_if_missing: bool = False, torch_compat: bool | None = None) -> C.
                                               c_int_p, c_double_pp, c_int_p, c_double_pp, C.POINTER(ScattResult)]
         lib.ndpp_grid_error.argtypes = [C.c_int, C.c_int, C.c_int, c_double_p, c_double_p, c_double_p, c_double_p,
                                         c_double_p, c_int_p]
+        lib.ndpp_thin_segments.argtypes = [C.c_int, C.c_int, C.c_int, c_double_p, c_double_p, c_double_p, C.c_int,
+                                           c_double_p, C.c_int, c_double_p]
+        lib.ndpp_thin_bounded.argtypes = [C.c_int, C.c_int, C.c_int, c_double_p, c_double_p, c_double_p, C.c_int,
+                                          c_double_p, C.c_double, C.c_int, c_int_p, c_int_p, c_double_p]
     _lib = lib
     return lib
 
@@ -968,6 +973,42 @@ def grid_error(x, y, x_mid, y_mid):
     err, arg = np.zeros(max(n - 1, 0)), np.zeros(max(n - 1, 0), dtype=np.int32)
     _check(load().ndpp_grid_error(L, G, n, _dp(x), _dp(y), _dp(x_mid), _dp(y_mid), _dp(err), _ip(arg)))
     return err, arg
+
+
+def _thin_args(x, y, y2, tokeep):
+    x, y = _f64(x), _f64(y)
+    if y.ndim != 3 or len(x) != y.shape[0]:
+        raise ValueError(f"x must be (n,) and y (n, G, L), got {x.shape} and {y.shape}")
+    y2 = None if y2 is None else _f64(y2)
+    if y2 is not None and y2.shape != y.shape:
+        raise ValueError(f"y2 must have y's shape {y.shape}, got {y2.shape}")
+    return x, y, y2, _f64(np.zeros(0) if tokeep is None else tokeep).ravel()
+
+
+def thin_segments(x, y, y2=None, tokeep=None, window: int = 32) -> np.ndarray:
+    """ndpp_thin_segments: seg_err[n][window-1], the worst error of the points strictly inside every
+    segment (a, a+d), d = 2..window, of the grid x[n] with rows y[n][G][L] (and y2 alike) against the
+    interpolation between its end rows (include/ndpp_hip.h).  -1: the segment ends beyond the grid;
+    inf: a must-keep point (an x equal to a tokeep entry) inside, or a value that is not finite."""
+    x, y, y2, tokeep = _thin_args(x, y, y2, tokeep)
+    n, G, L = y.shape
+    seg = np.zeros((n, max(int(window) - 1, 1)))
+    _check(load().ndpp_thin_segments(L, G, n, _dp(x), _dp(y), None if y2 is None else _dp(y2), len(tokeep),
+                                     _dp(tokeep) if len(tokeep) else None, int(window), _dp(seg)))
+    return seg
+
+
+def thin_bounded(x, y, y2=None, tokeep=None, tol: float = 1.0e-3, window: int = 32):
+    """ndpp_thin_bounded: (kept indices, max_err) of the chain over ndpp_thin_segments at tol.  Every
+    dropped point is within max_err <= tol of the interpolation between its two kept neighbours;
+    nothing is moved: gather the rows with the indices."""
+    x, y, y2, tokeep = _thin_args(x, y, y2, tokeep)
+    n, G, L = y.shape
+    kept, n_kept, max_err = np.zeros(max(n, 1), dtype=np.int32), C.c_int(), C.c_double()
+    _check(load().ndpp_thin_bounded(L, G, n, _dp(x), _dp(y), None if y2 is None else _dp(y2), len(tokeep),
+                                    _dp(tokeep) if len(tokeep) else None, float(tol), int(window), _ip(kept),
+                                    C.byref(n_kept), C.byref(max_err)))
+    return kept[:n_kept.value].copy(), max_err.value
 
 
 def scatt_nuclide(params: Params, nuclide, e_bins, nuscatt: bool = True):

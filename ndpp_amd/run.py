@@ -34,7 +34,15 @@ input error):
                        TOL is reported as unresolved.  With --check-grid the refined grids are
                        what is checked.
   --check-tol X        the tolerance --check-grid counts intervals against (default: TOL of
-                       --refine-grid, else 1e-3); an input error without --check-grid."""
+                       --refine-grid, else 1e-3); an input error without --check-grid.
+  --thin-grid TOL      before print_tol / thinning / writing, and after --refine-grid when both are
+                       given, drop the points of the neutron tables' grids that interpolation between
+                       the kept neighbours reproduces to TOL under the same metric (ndpp_amd.thin;
+                       --thin-window W, default 32, the longest run of points one segment may skip,
+                       2..64).  Group edges, the free-gas cutoff and the reaction thresholds are
+                       kept.  Thermal tables and chi grids are not thinned.  With --check-grid the
+                       thinned grids are what is checked.  `thinning_tol` of ndpp.xml -- the
+                       reference's rule, the thin_tol of the file header -- is independent of it."""
 from __future__ import annotations
 
 import argparse
@@ -48,7 +56,7 @@ from pathlib import Path
 
 import numpy as np
 
-from . import ace, grid, gridcheck, lib
+from . import ace, grid, gridcheck, lib, thin
 
 EXIT_OK, EXIT_INPUT, EXIT_LIBRARY = 0, 2, 3
 
@@ -282,7 +290,7 @@ def _device_ms() -> float:
 def compute(s: dict, tables: list, grid_opts: dict | None = None) -> tuple:
     """Every table's file bytes, its timing record and the grid report: ([(file name, bytes)],
     [record], report).  The report is None without grid_opts (check, check_tol, refine_tol,
-    max_passes, max_growth)."""
+    max_passes, max_growth, thin_tol, thin_window)."""
     p, o, bins = params_of(s), options_of(s), s["energy_bins"]
     tab = s["scatt_type"] == "tabular"
     files, recs = [None] * len(tables), [None] * len(tables)
@@ -308,6 +316,16 @@ def compute(s: dict, tables: list, grid_opts: dict | None = None) -> tuple:
                    for k, t in enumerate(tables)]
             grid_rep = dict(refine=dict(tol=go["refine_tol"], max_passes=go["max_passes"],
                                         max_growth=go["max_growth"], wall_s=time.perf_counter() - t1, tables=rep))
+        if go.get("thin_tol") is not None:
+            t1 = time.perf_counter()
+            res, rep = thin.thin_results(p, bins, [tables[k] for k in neut], res, s["nuscatter"], go["thin_tol"],
+                                         go["thin_window"])
+            by_table = dict(zip(neut, rep))
+            rep = [by_table.get(k) or dict(name=t["listing"]["name"], kind=t["kind"], sections={},
+                                           note="thermal table: not thinned")
+                   for k, t in enumerate(tables)]
+            grid_rep = dict(grid_rep or {}, thin=dict(tol=go["thin_tol"], window=go["thin_window"],
+                                                      wall_s=time.perf_counter() - t1, tables=rep))
         for k, r in zip(neut, res):
             raw[k] = r
             t = tables[k]
@@ -410,7 +428,7 @@ def run(run_dir, json_path=None, out=sys.stdout, grid_opts: dict | None = None) 
     try:
         s = read_ndpp_xml(run_dir)
         if grid_opts is not None and s["scatt_type"] == "tabular":
-            raise InputError("--check-grid and --refine-grid cover Legendre output only: the tabular rows of the "
+            raise InputError("--check-grid, --refine-grid and --thin-grid cover Legendre output only: the tabular rows of the "
                              "free-gas range do not settle, so an error measured on them would be the "
                              "quadrature's, not the grid's.")
         xs = read_cross_sections(s["cross_sections"])
@@ -448,6 +466,9 @@ def run(run_dir, json_path=None, out=sys.stdout, grid_opts: dict | None = None) 
                 print(f"{t['name']:>12s} {name:13s} refined to {grid_rep['refine']['tol']:g}: {g['points_before']} -> "
                       f"{g['points_after']} E_in in {g['passes']} passes ({g['stopped']}), {len(g['unresolved'])} "
                       f"unresolved ({sum(u['at_breakpoint'] for u in g['unresolved'])} at a breakpoint)", file=out)
+    if grid_rep and "thin" in grid_rep:
+        for line in thin.format_lines(grid_rep["thin"]["tables"], grid_rep["thin"]["tol"]):
+            print(line, file=out)
     if grid_rep and "check" in grid_rep:
         for line in gridcheck.format_lines(grid_rep["check"]["tables"]):
             print(line, file=out)
@@ -463,7 +484,9 @@ def _grid_options(a):
     """The grid flags as compute()'s grid_opts (None: no flag given).  Raises InputError."""
     if a.check_tol is not None and not a.check_grid:
         raise InputError("--check-tol is the tolerance of --check-grid: give both")
-    if not a.check_grid and a.refine_grid is None:
+    if a.thin_window is not None and a.thin_grid is None:
+        raise InputError("--thin-window is the window of --thin-grid: give both")
+    if not a.check_grid and a.refine_grid is None and a.thin_grid is None:
         return None
 
     def positive(flag, text):
@@ -481,8 +504,12 @@ def _grid_options(a):
         raise InputError(f"--max-passes {a.max_passes}: must not be negative")
     if not (a.max_growth >= 1.0):
         raise InputError(f"--max-growth {a.max_growth}: must be at least 1")
+    thin_tol = None if a.thin_grid is None else positive("--thin-grid", a.thin_grid)
+    window = 32 if a.thin_window is None else a.thin_window
+    if not 2 <= window <= 64:
+        raise InputError(f"--thin-window {window}: must be between 2 and 64")
     return dict(check=bool(a.check_grid), check_tol=ctol, refine_tol=tol, max_passes=a.max_passes,
-                max_growth=a.max_growth)
+                max_growth=a.max_growth, thin_tol=thin_tol, thin_window=window)
 
 
 def main(argv=None) -> int:
@@ -501,6 +528,11 @@ def main(argv=None) -> int:
                     help="a grid stops refining before it exceeds this multiple of its length (default 4)")
     ap.add_argument("--check-tol", metavar="X", default=None,
                     help="tolerance --check-grid counts intervals against (default: TOL, else 1e-3)")
+    ap.add_argument("--thin-grid", metavar="TOL", default=None,
+                    help="drop the grid points of the neutron tables that interpolation between their kept "
+                         "neighbours reproduces to TOL")
+    ap.add_argument("--thin-window", metavar="W", type=int, default=None,
+                    help="points one thinned segment may span, 2..64 (default 32)")
     a = ap.parse_args(argv)
     try:
         grid_opts = _grid_options(a)
