@@ -715,6 +715,43 @@ int ndpp_thin_bounded(int L, int G, int n, const double *x, const double *y, con
                       int n_keep, const double *tokeep, double tol, int window,
                       int *kept /* [n] */, int *n_kept, double *max_err);
 
+/* ---- distance between two sections on different incoming-energy grids.
+ * Replaces nothing: the reference never compares two libraries.  Section A: xa[na] with rows
+ * ya[na][G][La]; section B: xb[nb] with rows yb[nb][G][Lb]; the same G outgoing groups, and the
+ * first Lc = min(La, Lb) entries of every group are compared (a P5 library against a P10 one).  Both
+ * grids strictly increasing, positive and finite.  A consumer reads a section linearly in ln E
+ * (thin_grid's rule): for a query x = xq[q] inside both grids' ranges, with i the largest index with
+ * xa[i] <= x and i1 = min(i + 1, na - 1),
+ *   fa   = ln(x / xa[i]) / ln(xa[i+1] / xa[i])      (0 when x == xa[i]; the host's log)
+ *   A(x) = ya[i] + (ya[i1] - ya[i]) * fa
+ * and B(x) alike with j, j1 and fb.  Then, for e = (g, l), g < G, l < Lc,
+ *   d_e    = | A(x)_e - B(x)_e |
+ *   scale  = max over g of |P0| (l = 0) in the rows ya[i], ya[i1], yb[j], yb[j1]
+ *   err[q] = max over e of d_e / scale               (0 when scale is 0)
+ *   arg[q] = g * Lc + l of the maximum, the lowest on a tie.
+ * A NaN or an infinity in an element involved, or in what it produces, gives err[q] = +inf and
+ * arg[q] = the lowest such e.  A query that is not positive and finite, or outside the range of
+ * either grid, is skipped: err = -1, arg = -1.  worst[g][l] (optional) = the maximum of d_e / scale
+ * over the queries that were not skipped: +inf if any of them gave a NaN or an infinity for that
+ * element, -1 if every query was skipped.
+ * Between two neighbouring points u, u' of the union of xa and xb both interpolants are linear in
+ * ln x and the scale is constant on [u, u'), so the supremum of err there is err(u) or the limit of
+ * err from below u' (the scale jumps at u', where a grid moves on to its next rows): queried at the
+ * union points and at the largest double below each (ndpp_amd/compare.py: union_queries), max err
+ * is the distance of the two sections, not a sample of it.
+ * i, fa, j, fb come from the host; + - * / fabs and comparisons run on the device in the order
+ * written, without contraction: a host restatement reproduces err, arg and worst bit for bit
+ * (ndpp_amd/compare.py: compare_numpy).
+ * NDPP_EINVAL, decided before the device is touched: G, La or Lb < 1, na or nb < 2, nq < 1, a NULL
+ * pointer (worst may be NULL), a grid that is not strictly increasing, positive and finite, a
+ * G * max(La, Lb) that does not fit an index.  Without a device NDPP_EDEVICE.                      */
+int ndpp_lib_compare(int G, int La, int Lb,
+                     int na, const double *xa, const double *ya /* [na][G][La] */,
+                     int nb, const double *xb, const double *yb /* [nb][G][Lb] */,
+                     int nq, const double *xq,
+                     double *err /* [nq] */, int *arg /* [nq] */,
+                     double *worst /* [G][min(La,Lb)], may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,7 +15,7 @@ from .lib import (_check, Params, Stats, NdppError, load, library_path, mu_grid,
                   Positivity, scatt_positivity, expand_moments,
                   SCATT_LEGENDRE, SCATT_TABULAR, MAX_TAB_BINS, elastic_tab_batch, file6_tab_batch,
                   law9_tab_batch, scatt_nuclide_tab, scatt_library_tab, scatt_library_at, grid_error,
-                  thin_segments, thin_bounded)
+                  thin_segments, thin_bounded, lib_compare)
 from .scatt import binary_search, elastic_brackets, calc_elastic_grid  # noqa: F401
 
 __version__ = "0.2.0"

@@ -46,7 +46,7 @@ EXPORTS = [
     "ndpp_scatt_positivity", "ndpp_expand_moments",
     "ndpp_elastic_tab_batch", "ndpp_file6_tab_batch", "ndpp_law9_tab_batch", "ndpp_scatt_nuclide_tab",
     "ndpp_scatt_library_tab", "ndpp_scatt_library_at", "ndpp_grid_error",
-    "ndpp_thin_segments", "ndpp_thin_bounded",
+    "ndpp_thin_segments", "ndpp_thin_bounded", "ndpp_lib_compare",
 ]
 
 
@@ -591,6 +591,8 @@ def load(build_if_missing: bool = False, torch_compat: bool | None = None) -> C.
                                            c_double_p, C.c_int, c_double_p]
         lib.ndpp_thin_bounded.argtypes = [C.c_int, C.c_int, C.c_int, c_double_p, c_double_p, c_double_p, C.c_int,
                                           c_double_p, C.c_double, C.c_int, c_int_p, c_int_p, c_double_p]
+        lib.ndpp_lib_compare.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, c_double_p, c_double_p, C.c_int,
+                                         c_double_p, c_double_p, C.c_int, c_double_p, c_double_p, c_int_p, c_double_p]
     _lib = lib
     return lib
 
@@ -973,6 +975,25 @@ def grid_error(x, y, x_mid, y_mid):
     err, arg = np.zeros(max(n - 1, 0)), np.zeros(max(n - 1, 0), dtype=np.int32)
     _check(load().ndpp_grid_error(L, G, n, _dp(x), _dp(y), _dp(x_mid), _dp(y_mid), _dp(err), _ip(arg)))
     return err, arg
+
+
+def lib_compare(xa, ya, xb, yb, xq):
+    """ndpp_lib_compare: at every query xq[nq] the largest difference between the rows interpolated,
+    linearly in ln E, from section A (xa[na], ya[na][G][La]) and from section B (xb[nb], yb[nb][G][Lb]),
+    over the P0 scale of the four rows involved (include/ndpp_hip.h).  Returns (err[nq], arg[nq],
+    worst[G][min(La, Lb)]); err -1: skipped (outside either grid), inf: not finite."""
+    xa, ya, xb, yb, xq = _f64(xa), _f64(ya), _f64(xb), _f64(yb), _f64(xq).ravel()
+    if ya.ndim != 3 or yb.ndim != 3 or ya.shape[1] != yb.shape[1]:
+        raise ValueError(f"ya and yb must be (n, G, L) with the same G, got {ya.shape} and {yb.shape}")
+    if xa.shape != (ya.shape[0],) or xb.shape != (yb.shape[0],):
+        raise ValueError(f"shapes do not match: xa {xa.shape}, ya {ya.shape}, xb {xb.shape}, yb {yb.shape}")
+    (na, G, La), (nb, _, Lb) = ya.shape, yb.shape
+    nq = len(xq)
+    err, arg = np.zeros(max(nq, 1)), np.zeros(max(nq, 1), dtype=np.int32)
+    worst = np.zeros((G, min(La, Lb)))
+    _check(load().ndpp_lib_compare(G, La, Lb, na, _dp(xa), _dp(ya), nb, _dp(xb), _dp(yb), nq, _dp(xq), _dp(err),
+                                   _ip(arg), _dp(worst)))
+    return err[:nq], arg[:nq], worst
 
 
 def _thin_args(x, y, y2, tokeep):
