@@ -657,6 +657,62 @@ def file6_tunables(R, M, mu):
     return res
 
 
+def file4_edge_cases():
+    """The cases of file4_cm_edges.npz: every combination of synth.file4_matrix() (so every value of
+    M, L, G and the kinematics), each at three of its ten incoming energies and with one of the
+    table kinds, both rotating with the case number so that every energy position and every kind
+    occurs.  Above M = 129 only the kinds whose values take + - * / and comparisons are used: those
+    are rebuilt from the kind alone with the same bits everywhere, while exp() and the random
+    generator may differ between numpy builds; up to M = 129 the tables themselves are stored."""
+    sys.path.insert(0, str(HERE.parent))
+    from synth import (FILE4_EXACT_KINDS, FILE4_KINDS, FILE4_M, FILE4_TOP_AWR, file4_batch, file4_matrix,
+                       file4_tables, file4_top_inputs, mu_grid as synth_mu_grid)
+    cases = []
+    for k, (M, L, G, A, Q) in enumerate(file4_matrix()):
+        c = file4_batch(M, L, G, A, Q)
+        kind = k % len(FILE4_KINDS) if M <= 129 else FILE4_EXACT_KINDS[k % len(FILE4_EXACT_KINDS)]
+        for e in sorted({k % 10, (k + 3) % 10, (k + 7) % 10}):
+            cases.append(dict(M=M, L=L, G=G, A=A, Q=Q, kind=kind, Ein=float(c["ein"][e]), c=c, top=0))
+    # synth.file4_top_inputs: a bound below +1 in cell M, where the top-of-grid branch's value counts
+    for M in FILE4_M:
+        ein, bins = file4_top_inputs(M)
+        mu = synth_mu_grid(M)
+        c = dict(mu=mu, f_tab=file4_tables(mu, M), bins=bins)
+        for E in ein:
+            for kind in (range(len(FILE4_KINDS)) if M <= 129 else FILE4_EXACT_KINDS):
+                cases.append(dict(M=M, L=11, G=len(bins) - 1, A=FILE4_TOP_AWR, Q=0.0, kind=kind, Ein=float(E),
+                                  c=c, top=1))
+    return cases
+
+
+def file4_edge_goldens(R):
+    """integrate_file4_cm_leg (scattdata_header.F90:956) of the flang build beyond mu_bins = 2001:
+    the top-of-grid cell, all orders, 1..300 groups, R < 1, thresholds, Q > 0, tables that are not
+    smooth.  Inputs are stored compactly: per case M, L, G, awr, Q, E_in, the table's kind and the
+    seed of synth.file4_tables (the random kind's; M by convention); each group structure once
+    (bins_<G>, bins_top_<M> for the cases with top = 1); the tables once per M <= 129 (tab_<M>: all
+    kinds, not the random one alone, since exp() need not have the same bits with every numpy)."""
+    cases = file4_edge_cases()
+    out, extra = [], {}
+    for c in cases:
+        M, L, G = c["M"], c["L"], c["G"]
+        b = c["c"]
+        fw = np.ascontiguousarray(b["f_tab"][c["kind"]])
+        o = np.zeros((G, L))
+        R.ref_integrate_file4_cm_leg(dp(fw), c["Ein"], c["A"], c["Q"], dp(b["bins"]), G + 1, dp(b["mu"]), M, L, dp(o))
+        assert np.isfinite(o).all()
+        out.append(o.ravel())
+        extra[f"bins_top_{M}" if c["top"] else f"bins_{G}"] = b["bins"]
+        if M <= 129:
+            extra[f"tab_{M}"] = b["f_tab"]
+    col = lambda key, dt: np.array([c[key] for c in cases], dtype=dt)
+    np.savez_compressed(HERE / "file4_cm_edges.npz", n=len(cases), M=col("M", np.int32), L=col("L", np.int32),
+                        G=col("G", np.int32), A=col("A", np.float64), Q=col("Q", np.float64),
+                        kind=col("kind", np.int32), Ein=col("Ein", np.float64), top=col("top", np.int32),
+                        seed=col("M", np.int32), out=np.concatenate(out), **extra)
+    print(f"file4_cm_edges: {len(cases)} calls, {sum(len(o) for o in out)} moments")
+
+
 def main():
     if not REF.exists():
         sys.exit(f"{REF} missing: run `make -C oracle ref` first")
@@ -717,6 +773,7 @@ def main():
         fb=np.array([0.3 * ((k % 13) % 3) for k in range(len(cases))]),
         out=np.concatenate([c["out"].ravel() for c in cases]))
 
+    file4_edge_goldens(R)
     file6_goldens(R)
     sab_goldens(R)
     chi_goldens(R)
@@ -753,6 +810,8 @@ if __name__ == "__main__":
         library_goldens(load_ref())
     elif len(sys.argv) > 1 and sys.argv[1] == "library":
         library_goldens(load_ref())
+    elif len(sys.argv) > 1 and sys.argv[1] == "file4_edges":
+        file4_edge_goldens(load_ref())
     elif len(sys.argv) > 1 and sys.argv[1] == "tunables":
         tunables_goldens(load_ref())
     else:

@@ -518,3 +518,164 @@ def synthetic_library(n_nuclides=423, n_thermal=20, n_fissionable=30, seed=2024,
     fissionable = list(range(n_nuclides - n_fissionable, n_nuclides))
     chis = [chi_case(seed=seed + 500 + k) for k in range(n_fissionable)]
     return dict(awr=awr, nuclides=nucs, thermal=thermal, fissionable=fissionable, chi=chis)
+
+
+# ---- file-4 two-body kinematics (integrate_file4_cm_leg) beyond mu_bins = 2001 -------------
+FILE4_M = (5, 64, 65, 129, 1000, 2001)
+FILE4_L = (1, 3, 4, 5, 6, 7, 8, 9, 10, 11)          # every LMAX template (4, 6, 8, 11) and L below it
+FILE4_G = (1, 2, 63, 64, 65, 128, 129, 300)
+FILE4_KINDS = ("quadratic", "step", "kink", "ramp", "exp", "random", "negative", "negative kink")
+# the kinds whose values need + - * / and comparisons only: the same bits with every numpy
+FILE4_EXACT_KINDS = (0, 1, 2, 3, 6, 7)
+
+
+def file4_tables(mu, seed):
+    """The f(mu) tables of FILE4_KINDS as consecutive rows, [8][len(mu)]: smooth quadratic, step at
+    0.2137, kink, a run of zeros followed by a ramp, a forward peak, seeded uniform random, and
+    the quadratic and the kink negated.  The last two are no distributions: with them a
+    zero-width piece at mu = 1 gives -0.0 in both rows of a blend, so a group that the reference
+    skips (+0.0) and a kernel does not differs in the sign bit, which the tests compare.
+    Adjacent rows are unlike, so a blend of rows k and k + 1 mixes two shapes."""
+    rng = np.random.default_rng(seed)
+    return np.ascontiguousarray(np.stack([
+        0.5 * (1 + 0.4 * mu + 0.3 * (1.5 * mu * mu - 0.5)),
+        np.where(mu < 0.2137, 0.25, 1.0),
+        np.abs(mu - 0.3331) + 0.05,
+        np.maximum(0.0, mu - 0.5),
+        np.exp(8.0 * (mu - 1.0)),
+        rng.uniform(0.0, 1.0, len(mu)),
+        -0.5 * (1 + 0.4 * mu + 0.3 * (1.5 * mu * mu - 0.5)),
+        -(np.abs(mu - 0.3331) + 0.05)]))
+
+
+def file4_kinematics():
+    """(awr, Q): R < 1 (awr < 1), hydrogen, awr = 1 exactly, two thresholds (light and heavy),
+    heavy elastic, exothermic."""
+    return [(0.5, 0.0), (0.999167, 0.0), (1.0, 0.0), (15.8575, -6.05), (236.0058, -0.0449),
+            (236.0058, 0.0), (26.75, 1.2)]
+
+
+def file4_bins(G):
+    """G = 1: [0, 20]; G = 2: the shipped two-group structure; else the fine structures
+    [0] + geomspace(1e-9, 20, G)."""
+    if G == 1:
+        return np.array([0.0, 20.0])
+    if G == 2:
+        return np.array([0.0, 6.25e-7, 20.0])
+    bins = np.concatenate([[0.0], np.geomspace(1e-9, 20.0, G)])
+    bins[-1] = 20.0
+    return bins
+
+
+def file4_threshold(awr, Q):
+    return -Q * (awr + 1.0) / awr if Q < 0.0 else 0.0
+
+
+def file4_energies(awr, Q, n_ladder=7):
+    """Incoming energies of one file-4 call, never below the threshold (there the reference takes
+    the square root of a negative number): a geometric ladder from max(1e-6, thr (1 + 1e-7)) to
+    19.5, that lower end times 1.0000001, the top bin edge 20 and 25 above it."""
+    lo = max(1e-6, file4_threshold(awr, Q) * (1.0 + 1e-7))
+    return np.concatenate([np.geomspace(lo, 19.5, n_ladder), [lo * 1.0000001, 20.0, 25.0]])
+
+
+def file4_matrix():
+    """The (M, L, G, awr, Q) combinations that the oracle-vs-Fortran sweep and the GPU tests share:
+    every (M, L) pair, 60 cases; case k = 10 iM + iL takes the (G, kinematics) pair number
+    11 k mod 56 of the 8 x 7 pairs in row-major order.  11 and 56 are coprime, so cases 0..55
+    visit every (G, kinematics) pair once and the last four visit four of them again."""
+    kin = file4_kinematics()
+    cases = []
+    for iM, M in enumerate(FILE4_M):
+        for iL, L in enumerate(FILE4_L):
+            pair = (11 * (10 * iM + iL)) % (len(FILE4_G) * len(kin))
+            G, (awr, Q) = FILE4_G[pair // len(kin)], kin[pair % len(kin)]
+            cases.append((M, L, G, awr, Q))
+    return cases
+
+
+def file4_batch(M, L, G, awr, Q):
+    """Inputs of one elastic_leg_batch call of the matrix: the eight tables, the energies and, per
+    energy, a random lower row and a blend weight in [0, 1] with exactly 0 and exactly 1 among
+    them.  Seeded by the combination (the random table by M alone), so every caller sees the same
+    numbers."""
+    seed = 1000003 * M + 10007 * L + 101 * G + int(1000 * awr) + int(100 * abs(Q))
+    rng = np.random.default_rng(seed)
+    mu = mu_grid(M)
+    ein = file4_energies(awr, Q)
+    row_lo = rng.integers(0, len(FILE4_KINDS) - 1, len(ein)).astype(np.int32)
+    w_hi = rng.uniform(0.0, 1.0, len(ein))
+    w_hi[1], w_hi[-2] = 0.0, 1.0
+    row_lo[[0, 4]] = len(FILE4_KINDS) - 2        # the two negative rows blended: -0.0 can come out
+    return dict(mu=mu, f_tab=file4_tables(mu, M), bins=file4_bins(G), ein=ein, row_lo=row_lo, w_hi=w_hi)
+
+
+def file4_bound_classes(M, awr, Q, Ein, bins):
+    """file4_bounds of the kernel (scattdata_header.F90:986-1015) restated: per group the clamped
+    CM cosines and 1-based cells of its two bounds.  Returns (wlo, whi, ilo, ihi)."""
+    mu = mu_grid(M)
+    dw = mu[1] - mu[0]
+    R = awr * np.sqrt(1.0 + Q * (awr + 1.0) / (awr * Ein))
+    a, b, c = (1.0 + awr) * (1.0 + awr), 1.0 + R * R, 0.5 / (R * Ein)
+    w = np.clip((np.asarray(bins) * a - Ein * b) * c, -1.0, 1.0)
+    iw = ((w + 1.0) / dw).astype(np.int64) + 1
+    return w[:-1], w[1:], iw[:-1], iw[1:]
+
+
+def file4_golden_cases(g, M=None):
+    """The calls recorded in tests/golden/file4_cm_edges.npz (g: the loaded file), optionally
+    those of one M: (M, L, G, awr, Q, Ein, kind, fw, bins, what the Fortran returned [G][L]).
+    Tables up to M = 129 and the group structures are read from the file; the larger tables are
+    of the kinds that are rebuilt exactly (FILE4_EXACT_KINDS)."""
+    off = 0
+    for k in range(int(g["n"])):
+        Mk, L, G, kind = int(g["M"][k]), int(g["L"][k]), int(g["G"][k]), int(g["kind"][k])
+        ref = g["out"][off:off + G * L].reshape(G, L)
+        off += G * L
+        if M is not None and Mk != M:
+            continue
+        if Mk <= 129:
+            fw = g[f"tab_{Mk}"][kind]
+        else:
+            assert kind in FILE4_EXACT_KINDS
+            fw = file4_tables(mu_grid(Mk), int(g["seed"][k]))[kind]
+        if int(g["top"][k]):
+            bins = g[f"bins_top_{Mk}"]
+        else:
+            bins = g[f"bins_{G}"]
+        yield (Mk, L, G, float(g["A"][k]), float(g["Q"][k]), float(g["Ein"][k]), kind,
+               np.ascontiguousarray(fw), np.ascontiguousarray(bins), ref)
+
+
+FILE4_TOP_AWR = 15.8575
+
+
+def file4_top_inputs(M):
+    """Inputs on which the VALUE the top-of-grid branch returns can be seen.  Where a bound is
+    clamped to +1 the branch's value is multiplied by the zero width 1 - mu[M - 1]; it counts
+    only when a bound BELOW +1 lands in cell M: within rounding of +1, so that (w + 1) / dw
+    rounds up to M - 1.  For elastic scattering w(E') = 1 at E' = E_in, so the bin edges tried are
+    E_in stepped down by a few ulps, for awr = 15.8575; kept are those whose cosine is below 1 and
+    in cell M (found by the restated bounds, IEEE arithmetic only: the same everywhere).
+    Returns (ein, bins): the energies that have such an edge, and [0, those edges, 20].  The
+    group above such an edge is one piece [w, 1] of width ~1e-16 that starts in cell M; the group
+    below it ends there, at a cosine left of the grid's last point (a last piece of negative
+    width, as in the reference).  Nothing for M = 2001: there +1 itself is in cell M - 1."""
+    ein, edges = [], []
+    for Ein in (1e-3, 0.7, 1.5, 3.3, 12.0):
+        e = Ein
+        for _ in range(8):
+            e = float(np.nextafter(e, 0.0))
+            wlo, _, ilo, _ = file4_bound_classes(M, FILE4_TOP_AWR, 0.0, Ein, np.array([e, 20.0]))
+            if wlo[0] < 1.0 and ilo[0] == M:
+                ein.append(Ein)
+                edges.append(e)
+                break
+    return np.array(ein), np.concatenate([[0.0], edges, [20.0]])
+
+
+def same_bits(a, b):
+    """a and b have the same shape and the same bit patterns: np.array_equal that also tells -0.0
+    from +0.0 (and takes equal NaNs as equal)."""
+    a, b = np.ascontiguousarray(a, dtype=np.float64), np.ascontiguousarray(b, dtype=np.float64)
+    return a.shape == b.shape and bool((a.view(np.uint64) == b.view(np.uint64)).all())

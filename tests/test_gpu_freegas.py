@@ -61,16 +61,15 @@ def test_file4_vs_golden(hip):
         ref = g["out"][oo:oo + G * L].reshape(G, L)
         ob += nb
         oo += G * L
-        if k % 3:
-            continue
         fw = 0.5 * (1 + g["fa"][k] * mu + g["fb"][k] * (1.5 * mu * mu - 0.5))
         got = hip.integrate_file4_cm_leg(fw, float(g["Ein"][k]), float(g["A"][k]),
                                          float(g["Q"][k]), bins, mu, L).T
         exact += int(np.array_equal(got, ref))
         worst = max(worst, scale_rel_err(got[None], ref[None]))
-    print(f"file4: worst scale-rel err {worst:.3e}, bit-identical cases {exact}")
-    # only + - * / sqrt, all IEEE on gfx950 -> expected bit-identical
+    print(f"file4: worst scale-rel err {worst:.3e}, bit-identical cases {exact} of {int(g['n'])}")
+    # only + - * / sqrt, all IEEE on gfx950 -> bit-identical, every case
     assert worst < 1e-14
+    assert exact == int(g["n"])
 
 
 def test_file4_wave_kernel_is_the_per_group_kernel_bit_for_bit(hip, monkeypatch):

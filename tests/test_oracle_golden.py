@@ -6,6 +6,8 @@ import numpy as np
 import pytest
 
 from conftest import dp, ip, load_golden, oracle_params, scale_rel_err
+from synth import (FILE4_G, FILE4_KINDS, FILE4_L, FILE4_M, file4_golden_cases, file4_kinematics, mu_grid,
+                   same_bits)
 
 # The reference's own known answers that still pin the current API
 # (tests/test_scatt/test_scattdata.F90:1650,1687-1692 -- moments of a linear f
@@ -76,3 +78,24 @@ def test_file4_golden(oracle):
         oracle.oracle_integrate_file4_cm_leg(C.byref(p), dp(fw), float(g["Ein"][k]), float(g["A"][k]),
                                              float(g["Q"][k]), dp(bins), nb, dp(mu), dp(out))
         assert np.array_equal(out, ref), k
+
+
+def test_file4_edges_golden(oracle):
+    """file4_cm_edges.npz, written by the Fortran: small and odd cosine grids (a bound clamped to +1
+    falls in cell M), orders 1..11, 1..300 groups, R < 1, thresholds, Q > 0, rough tables.  The
+    oracle bit for bit, and the file holds every value of every axis."""
+    g = load_golden("file4_cm_edges")
+    seen = dict(M=set(), L=set(), G=set(), kin=set(), kind=set())
+    n = 0
+    for M, L, G, A, Q, Ein, kind, fw, bins, ref in file4_golden_cases(g):
+        mu = mu_grid(M)
+        p = oracle_params(oracle, L, M)
+        out = np.zeros((G, L))
+        oracle.oracle_integrate_file4_cm_leg(C.byref(p), dp(fw), Ein, A, Q, dp(bins), G + 1, dp(mu), dp(out))
+        assert same_bits(out, ref), (M, L, G, A, Q, Ein, FILE4_KINDS[kind])   # (the sign of a zero too)
+        for key, v in (("M", M), ("L", L), ("G", G), ("kin", (A, Q)), ("kind", kind)):
+            seen[key].add(v)
+        n += 1
+    assert n == int(g["n"])
+    assert seen["M"] == set(FILE4_M) and seen["L"] == set(FILE4_L) and seen["G"] >= set(FILE4_G)
+    assert seen["kin"] >= set(file4_kinematics()) and seen["kind"] == set(range(len(FILE4_KINDS)))

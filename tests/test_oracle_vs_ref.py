@@ -7,6 +7,8 @@ import numpy as np
 import pytest
 
 from conftest import dp, oracle_params
+from synth import (FILE4_KINDS, FILE4_M, FILE4_TOP_AWR, file4_batch, file4_matrix, file4_tables, file4_top_inputs,
+                   mu_grid, same_bits)
 
 
 def test_calc_pn_bit_identical(oracle, ref):
@@ -70,6 +72,36 @@ def test_file4_bit_identical(oracle, ref):
             ref.ref_integrate_file4_cm_leg(dp(fw), Ein, A, Q, dp(bins), G + 1, dp(mu), M, L, dp(a))
             oracle.oracle_integrate_file4_cm_leg(C.byref(p), dp(fw), Ein, A, Q, dp(bins), G + 1, dp(mu), dp(b))
             assert (a == b).all(), (A, Q, Ein)
+
+
+@pytest.mark.parametrize("M", FILE4_M)
+def test_file4_bit_identical_beyond_2001_bins(oracle, ref, M):
+    """scattdata_header.F90:956 on the matrix the GPU tests use (synth.file4_matrix): small and
+    odd cosine grids, on which a bound clamped to +1 falls in cell M (the top-of-grid branch and
+    the zero-width last piece), every order 1..11, one to 300 groups, R < 1, thresholds within
+    1e-7, an exothermic Q, and tables with a step, a kink, a run of zeros, a peak and noise.
+    Every table of every energy of every combination, the C restatement against the Fortran."""
+    calls = []
+    for M_, L, G, A, Q in file4_matrix():
+        if M_ == M:
+            c = file4_batch(M, L, G, A, Q)
+            calls.append((L, A, Q, c["ein"], c["f_tab"], c["bins"]))
+    # a bound below +1 in cell M: there the value of the top-of-grid branch counts
+    ein, bins = file4_top_inputs(M)
+    calls.append((11, FILE4_TOP_AWR, 0.0, ein, file4_tables(mu_grid(M), M), bins))
+    mu = mu_grid(M)
+    for L, A, Q, ein, f_tab, bins in calls:
+        G = len(bins) - 1
+        p = oracle_params(oracle, L, M)
+        for Ein in ein:
+            for k in range(len(FILE4_KINDS)):
+                fw = np.ascontiguousarray(f_tab[k])
+                a, b = np.zeros((G, L)), np.zeros((G, L))
+                ref.ref_integrate_file4_cm_leg(dp(fw), float(Ein), A, Q, dp(bins), G + 1, dp(mu), M, L, dp(a))
+                oracle.oracle_integrate_file4_cm_leg(C.byref(p), dp(fw), float(Ein), A, Q, dp(bins), G + 1,
+                                                     dp(mu), dp(b))
+                assert np.isfinite(a).all()
+                assert same_bits(a, b), (M, L, G, A, Q, Ein, FILE4_KINDS[k])   # (the sign of a zero too)
 
 
 def test_merge_with_repeated_tail_values(oracle, ref):
