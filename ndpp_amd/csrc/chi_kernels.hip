@@ -287,13 +287,6 @@ __global__ __launch_bounds__(64) void chi_kernel(ChiDev D) {
   }
 }
 
-#define CHI_TRY(expr)                                                             \
-  do {                                                                            \
-    hipError_t e_ = (expr);                                                       \
-    if (e_ != hipSuccess)                                                         \
-      return fail(NDPP_EDEVICE, "%s failed: %s", #expr, hipGetErrorString(e_));   \
-  } while (0)
-
 struct Pool {  // device copies of host arrays, freed together
   std::vector<void*> ptrs;
   ~Pool() { for (void* p : ptrs) dev_free(p); }
@@ -417,47 +410,45 @@ extern "C" int ndpp_chi_batch(const ndpp_chi_nuclide* nuc, int n_prompt,
                   nuc->n_grid - prompt[i].threshold + 1);
   }
   for (int i = 0; i < n_delay; ++i) { int rc = check_spectrum(delay[i], false, i); if (rc) return rc; }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-    return fail(NDPP_EDEVICE, "no HIP device available (libndpp_hip has no CPU path)");
+  if (int rc = require_device()) return rc;
 
   Pool pool;
   ChiDev D;
   D.nuc = *nuc;
-  CHI_TRY(pool.up(nuc->energy, nuc->n_grid, &D.nuc.energy));
-  CHI_TRY(pool.up(nuc->fission, nuc->n_grid, &D.nuc.fission));
-  CHI_TRY(pool.up(nuc->nu_t_data, nuc->n_nu_t, &D.nuc.nu_t_data));
-  CHI_TRY(pool.up(nuc->nu_d_data, nuc->n_nu_d, &D.nuc.nu_d_data));
-  CHI_TRY(pool.up(nuc->nu_d_precursor_data, nuc->n_prec_data, &D.nuc.nu_d_precursor_data));
+  NDPP_TRY(pool.up(nuc->energy, nuc->n_grid, &D.nuc.energy));
+  NDPP_TRY(pool.up(nuc->fission, nuc->n_grid, &D.nuc.fission));
+  NDPP_TRY(pool.up(nuc->nu_t_data, nuc->n_nu_t, &D.nuc.nu_t_data));
+  NDPP_TRY(pool.up(nuc->nu_d_data, nuc->n_nu_d, &D.nuc.nu_d_data));
+  NDPP_TRY(pool.up(nuc->nu_d_precursor_data, nuc->n_prec_data, &D.nuc.nu_d_precursor_data));
   std::vector<ndpp_chi_spectrum> hp(prompt, prompt + n_prompt), hd(delay, delay + n_delay);
   for (auto* vec : {&hp, &hd})
     for (auto& s : *vec) {
-      CHI_TRY(pool.up(s.data, s.n_data, &s.data));
-      CHI_TRY(pool.up(s.sigma, s.n_sigma, &s.sigma));
-      CHI_TRY(pool.up(s.pv_nbt, s.pv_n_regions, &s.pv_nbt));
-      CHI_TRY(pool.up(s.pv_int, s.pv_n_regions, &s.pv_int));
-      CHI_TRY(pool.up(s.pv_x, s.pv_n_pairs, &s.pv_x));
-      CHI_TRY(pool.up(s.pv_y, s.pv_n_pairs, &s.pv_y));
+      NDPP_TRY(pool.up(s.data, s.n_data, &s.data));
+      NDPP_TRY(pool.up(s.sigma, s.n_sigma, &s.sigma));
+      NDPP_TRY(pool.up(s.pv_nbt, s.pv_n_regions, &s.pv_nbt));
+      NDPP_TRY(pool.up(s.pv_int, s.pv_n_regions, &s.pv_int));
+      NDPP_TRY(pool.up(s.pv_x, s.pv_n_pairs, &s.pv_x));
+      NDPP_TRY(pool.up(s.pv_y, s.pv_n_pairs, &s.pv_y));
     }
-  CHI_TRY(pool.up(hp.data(), hp.size(), &D.prompt));
-  CHI_TRY(pool.up(hd.data(), hd.size(), &D.delay));
-  CHI_TRY(pool.up(e_bins, G + 1, &D.e_bins));
-  CHI_TRY(pool.up(e_grid, n_ein, &D.e_grid));
+  NDPP_TRY(pool.up(hp.data(), hp.size(), &D.prompt));
+  NDPP_TRY(pool.up(hd.data(), hd.size(), &D.delay));
+  NDPP_TRY(pool.up(e_bins, G + 1, &D.e_bins));
+  NDPP_TRY(pool.up(e_grid, n_ein, &D.e_grid));
   const size_t nrow = (size_t)n_ein * G;
-  CHI_TRY(pool.alloc(nrow, &D.scratch));
-  CHI_TRY(pool.alloc(nrow, &D.chi_t));
-  CHI_TRY(pool.alloc(nrow, &D.chi_p));
-  CHI_TRY(pool.alloc(nrow * std::max(n_delay, 1), &D.chi_d));
+  NDPP_TRY(pool.alloc(nrow, &D.scratch));
+  NDPP_TRY(pool.alloc(nrow, &D.chi_t));
+  NDPP_TRY(pool.alloc(nrow, &D.chi_p));
+  NDPP_TRY(pool.alloc(nrow * std::max(n_delay, 1), &D.chi_d));
   D.n_prompt = n_prompt; D.n_delay = n_delay; D.G = G; D.NE = n_ein;
   const int blocks = std::max(1, (n_ein + 63) / 64);
   GpuSpan span(nullptr, kProfChi);
   hipLaunchKernelGGL(chi_kernel, dim3(blocks), dim3(64), 0, 0, D);
   span.end();
-  CHI_TRY(hipGetLastError());
-  CHI_TRY(hipDeviceSynchronize());
-  CHI_TRY(hipMemcpy(chi_t, D.chi_t, sizeof(double) * nrow, hipMemcpyDeviceToHost));
-  CHI_TRY(hipMemcpy(chi_p, D.chi_p, sizeof(double) * nrow, hipMemcpyDeviceToHost));
+  NDPP_TRY(hipGetLastError());
+  NDPP_TRY(hipDeviceSynchronize());
+  NDPP_TRY(hipMemcpy(chi_t, D.chi_t, sizeof(double) * nrow, hipMemcpyDeviceToHost));
+  NDPP_TRY(hipMemcpy(chi_p, D.chi_p, sizeof(double) * nrow, hipMemcpyDeviceToHost));
   if (n_delay > 0)
-    CHI_TRY(hipMemcpy(chi_d, D.chi_d, sizeof(double) * nrow * n_delay, hipMemcpyDeviceToHost));
+    NDPP_TRY(hipMemcpy(chi_d, D.chi_d, sizeof(double) * nrow * n_delay, hipMemcpyDeviceToHost));
   return NDPP_OK;
 }

@@ -141,13 +141,6 @@ compare_fold_kernel(int GLc, int n_chunks, const double* __restrict__ part, doub
   worst[e] = w;
 }
 
-#define CMP_TRY(expr)                                                             \
-  do {                                                                            \
-    hipError_t e_ = (expr);                                                       \
-    if (e_ != hipSuccess)                                                         \
-      return fail(NDPP_EDEVICE, "%s failed: %s", #expr, hipGetErrorString(e_));   \
-  } while (0)
-
 int check_grid(const char* name, int n, const double* x) {
   for (int i = 0; i < n; ++i)
     if (!(std::isfinite(x[i]) && x[i] > 0.0 && (i == 0 || x[i] > x[i - 1])))
@@ -184,9 +177,7 @@ extern "C" int ndpp_lib_compare(int G, int La, int Lb, int na, const double* xa,
   if (rc != NDPP_OK) return rc;
   rc = check_grid("xb", nb, xb);
   if (rc != NDPP_OK) return rc;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-    return fail(NDPP_EDEVICE, "lib_compare: no HIP device available (libndpp_hip has no CPU path)");
+  if ((rc = require_device("lib_compare"))) return rc;
 
   // rows and weights per query; row -1 marks the queries that are skipped: not positive and finite, or
   // outside the range of either grid
@@ -213,37 +204,37 @@ extern "C" int ndpp_lib_compare(int G, int La, int Lb, int na, const double* xa,
 
   DevBuf<double> d_ya, d_yb, d_fa, d_fb, d_err, d_scale, d_part, d_worst;
   DevBuf<int> d_ia, d_ib, d_arg;
-  CMP_TRY(d_ya.upload(ya, (size_t)na * G * La));
-  CMP_TRY(d_yb.upload(yb, (size_t)nb * G * Lb));
-  CMP_TRY(d_ia.upload(ia.data(), ia.size()));
-  CMP_TRY(d_ib.upload(ib.data(), ib.size()));
-  CMP_TRY(d_fa.upload(fa.data(), fa.size()));
-  CMP_TRY(d_fb.upload(fb.data(), fb.size()));
-  CMP_TRY(d_err.alloc(nq));
-  CMP_TRY(d_arg.alloc(nq));
-  CMP_TRY(d_scale.alloc(nq));
+  NDPP_TRY(d_ya.upload(ya, (size_t)na * G * La));
+  NDPP_TRY(d_yb.upload(yb, (size_t)nb * G * Lb));
+  NDPP_TRY(d_ia.upload(ia.data(), ia.size()));
+  NDPP_TRY(d_ib.upload(ib.data(), ib.size()));
+  NDPP_TRY(d_fa.upload(fa.data(), fa.size()));
+  NDPP_TRY(d_fb.upload(fb.data(), fb.size()));
+  NDPP_TRY(d_err.alloc(nq));
+  NDPP_TRY(d_arg.alloc(nq));
+  NDPP_TRY(d_scale.alloc(nq));
   if (worst) {
-    CMP_TRY(d_part.alloc((size_t)chunks * GLc));
-    CMP_TRY(d_worst.alloc(GLc));
+    NDPP_TRY(d_part.alloc((size_t)chunks * GLc));
+    NDPP_TRY(d_worst.alloc(GLc));
   }
   {
     GpuSpan span(nullptr, -1);
     hipLaunchKernelGGL(compare_error_kernel, dim3(nblk((long)nq * 64, kThreads)), dim3(kThreads), 0, 0, nq, G, La, Lb,
                        Lc, na, nb, d_ya.p, d_yb.p, d_ia.p, d_fa.p, d_ib.p, d_fb.p, d_err.p, d_arg.p, d_scale.p);
-    CMP_TRY(hipGetLastError());
+    NDPP_TRY(hipGetLastError());
     if (worst) {
       hipLaunchKernelGGL(compare_worst_kernel, dim3(tiles, chunks / per_block), dim3(kThreads), 0, 0, nq, per, G, La,
                          Lb, Lc, na, nb, d_ya.p, d_yb.p, d_ia.p, d_fa.p, d_ib.p, d_fb.p, d_scale.p, d_part.p);
-      CMP_TRY(hipGetLastError());
+      NDPP_TRY(hipGetLastError());
       hipLaunchKernelGGL(compare_fold_kernel, dim3(nblk(GLc, kThreads)), dim3(kThreads), 0, 0, GLc, chunks, d_part.p,
                          d_worst.p);
     }
     span.end();
-    CMP_TRY(hipGetLastError());
-    CMP_TRY(hipDeviceSynchronize());
+    NDPP_TRY(hipGetLastError());
+    NDPP_TRY(hipDeviceSynchronize());
   }
-  CMP_TRY(d_err.download(err, nq));
-  CMP_TRY(d_arg.download(arg, nq));
-  if (worst) CMP_TRY(d_worst.download(worst, GLc));
+  NDPP_TRY(d_err.download(err, nq));
+  NDPP_TRY(d_arg.download(arg, nq));
+  if (worst) NDPP_TRY(d_worst.download(worst, GLc));
   return NDPP_OK;
 }

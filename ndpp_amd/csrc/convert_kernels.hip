@@ -187,15 +187,6 @@ int make_shape(const ndpp_ace_reaction* r, Shape& s) {
   return edist_shape(r, s);           // :240-254
 }
 
-
-
-#define CV_TRY(expr)                                                              \
-  do {                                                                            \
-    hipError_t e_ = (expr);                                                       \
-    if (e_ != hipSuccess)                                                         \
-      return fail(NDPP_EDEVICE, "%s failed: %s", #expr, hipGetErrorString(e_));   \
-  } while (0)
-
 // a job for convert_file4(iE) on the reaction's (or the fabricated isotropic) adist
 int adist_job(const ndpp_ace_reaction* r, const Shape& s, int iE, ColJob& j) {
   j = ColJob{COL_ZERO, 0, 0, 0, 0, 0, 0.0, 0.0};
@@ -264,9 +255,7 @@ static int convert_distro_impl(int mu_bins, const ndpp_ace_reaction* r, int G,
   if (NE != s.NE || total_np != (int)s.total_np)
     return fail(NDPP_EINVAL, "NE=%d total_np=%d but ndpp_scattdata_shape says %d, %ld", NE, total_np,
                 s.NE, s.total_np);
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-    return fail(NDPP_EDEVICE, "no HIP device available (libndpp_hip has no CPU path)");
+  if ((rc = require_device())) return rc;
 
   // ---- grid, outgoing-energy tables and one job per output column (host) ----
   std::vector<ColJob> jobs((size_t)total_np, ColJob{COL_ZERO, 0, 0, 0, 0, 0, 0.0, 0.0});
@@ -357,24 +346,24 @@ static int convert_distro_impl(int mu_bins, const ndpp_ace_reaction* r, int G,
   // ---- evaluate all columns on the device ----
   DevBuf<ColJob> d_jobs;
   DevBuf<double> d_a, d_e, d_f;
-  CV_TRY(d_jobs.upload(jobs.data(), jobs.size()));
+  NDPP_TRY(d_jobs.upload(jobs.data(), jobs.size()));
   {
     std::vector<double> pa((size_t)std::max(r->n_adist_data, 0) + 2, 0.0);
     std::vector<double> pe((size_t)std::max(r->n_edata, 0) + 2, 0.0);
     if (r->adist_data) std::copy(r->adist_data, r->adist_data + std::max(r->n_adist_data, 0), pa.begin() + 1);
     if (r->edata) std::copy(r->edata, r->edata + std::max(r->n_edata, 0), pe.begin() + 1);
-    CV_TRY(d_a.upload(pa.data(), pa.size()));
-    CV_TRY(d_e.upload(pe.data(), pe.size()));
+    NDPP_TRY(d_a.upload(pa.data(), pa.size()));
+    NDPP_TRY(d_e.upload(pe.data(), pe.size()));
   }
   const size_t nf = (size_t)total_np * mu_bins;
-  CV_TRY(d_f.alloc(nf));
+  NDPP_TRY(d_f.alloc(nf));
   GpuSpan span(nullptr, kProfConvert);
   hipLaunchKernelGGL(convert_kernel, dim3(nblk((long)nf, 256)), dim3(256), 0, 0, total_np,
                      make_mu_grid(mu_bins), d_jobs.p, d_a.p, d_e.p, d_f.p);
   span.end();
-  CV_TRY(hipGetLastError());
-  CV_TRY(hipDeviceSynchronize());
-  if (f) CV_TRY(hipMemcpy(f, d_f.p, sizeof(double) * nf, hipMemcpyDeviceToHost));
+  NDPP_TRY(hipGetLastError());
+  NDPP_TRY(hipDeviceSynchronize());
+  if (f) NDPP_TRY(hipMemcpy(f, d_f.p, sizeof(double) * nf, hipMemcpyDeviceToHost));
   if (keep) { *keep = d_f.p; d_f.p = nullptr; }
   return NDPP_OK;
 }

@@ -279,13 +279,6 @@ bool bytes_of(size_t a, size_t b, size_t c, size_t* out) {
   return !__builtin_mul_overflow(a, b, &ab) && !__builtin_mul_overflow(ab, c, out) && *out < ((size_t)1 << 62);
 }
 
-int no_device() {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-    return fail(NDPP_EDEVICE, "no HIP device available (libndpp_hip has no CPU path)");
-  return NDPP_OK;
-}
-
 // incoming energies per positivity block and the block size: whole energies per block, as few
 // idle lanes as possible (G = 7: 64 energies on 448 threads; G = 70: 7 on 512 -> 490 rows)
 void positivity_shape(int G, int* epb, int* threads) {
@@ -302,13 +295,6 @@ void positivity_shape(int G, int* epb, int* threads) {
   *epb = best_e;
   *threads = best_b;
 }
-
-#define EXP_TRY(expr)                                                             \
-  do {                                                                            \
-    hipError_t e_ = (expr);                                                       \
-    if (e_ != hipSuccess)                                                         \
-      return fail(NDPP_EDEVICE, "%s failed: %s", #expr, hipGetErrorString(e_));   \
-  } while (0)
 
 template <int NM>
 void launch_positivity(int nblk, int threads, int n_ein, int G, int L, int epb, const double* mat, int n_mu,
@@ -358,7 +344,7 @@ extern "C" int ndpp_scatt_positivity(int n_ein, int G, int L, const double* mat,
   if ((rc = check_mu("scatt_positivity", n_mu, mu))) return rc;
   *summary = ndpp_positivity{0, 0, INFINITY, -1, -1};
   if (n_ein == 0) return NDPP_OK;
-  if ((rc = no_device())) return rc;
+  if ((rc = require_device())) return rc;
 
   const std::vector<double> basis = make_basis(n_mu, mu, n_moments);
   int epb = 1, threads = 64;
@@ -372,17 +358,17 @@ extern "C" int ndpp_scatt_positivity(int n_ein, int G, int L, const double* mat,
   DevBuf<PosPart> d_part;
   DevBuf<long> d_boff;
   DevBuf<PosSum> d_sum;
-  EXP_TRY(d_mat.upload(mat, (size_t)n_ein * G * L));
-  EXP_TRY(d_basis.upload(basis.data(), basis.size()));
-  EXP_TRY(d_crow.alloc(2 * (size_t)slots));
-  EXP_TRY(d_cmin.alloc(slots));
-  EXP_TRY(d_cmu.alloc(slots));
-  EXP_TRY(d_part.alloc(nblk));
-  EXP_TRY(d_boff.alloc(nblk));
-  EXP_TRY(d_sum.alloc(1));
-  EXP_TRY(d_orow.alloc(2 * (size_t)n_out_max));
-  EXP_TRY(d_omin.alloc(n_out_max));
-  EXP_TRY(d_omu.alloc(n_out_max));
+  NDPP_TRY(d_mat.upload(mat, (size_t)n_ein * G * L));
+  NDPP_TRY(d_basis.upload(basis.data(), basis.size()));
+  NDPP_TRY(d_crow.alloc(2 * (size_t)slots));
+  NDPP_TRY(d_cmin.alloc(slots));
+  NDPP_TRY(d_cmu.alloc(slots));
+  NDPP_TRY(d_part.alloc(nblk));
+  NDPP_TRY(d_boff.alloc(nblk));
+  NDPP_TRY(d_sum.alloc(1));
+  NDPP_TRY(d_orow.alloc(2 * (size_t)n_out_max));
+  NDPP_TRY(d_omin.alloc(n_out_max));
+  NDPP_TRY(d_omu.alloc(n_out_max));
   {
     GpuSpan span(nullptr, -1);
     kPosLaunch[n_moments - 1](nblk, threads, n_ein, G, L, epb, d_mat.p, n_mu, d_basis.p, d_part.p, d_crow.p,
@@ -392,16 +378,16 @@ extern "C" int ndpp_scatt_positivity(int n_ein, int G, int L, const double* mat,
       hipLaunchKernelGGL(positivity_gather, dim3(nblk), dim3(256), 0, 0, slot_stride, n_out_max, d_part.p,
                          d_boff.p, d_crow.p, d_cmin.p, d_cmu.p, d_orow.p, d_omin.p, d_omu.p);
     span.end();
-    EXP_TRY(hipGetLastError());
-    EXP_TRY(hipDeviceSynchronize());
+    NDPP_TRY(hipGetLastError());
+    NDPP_TRY(hipDeviceSynchronize());
   }
   PosSum s;
-  EXP_TRY(hipMemcpy(&s, d_sum.p, sizeof(s), hipMemcpyDeviceToHost));
+  NDPP_TRY(hipMemcpy(&s, d_sum.p, sizeof(s), hipMemcpyDeviceToHost));
   const long n_out = std::min<long>(n_out_max, s.neg);
   if (n_out > 0) {
-    EXP_TRY(hipMemcpy(neg_rows, d_orow.p, 2 * sizeof(int) * n_out, hipMemcpyDeviceToHost));
-    if (neg_min) EXP_TRY(hipMemcpy(neg_min, d_omin.p, sizeof(double) * n_out, hipMemcpyDeviceToHost));
-    if (neg_mu) EXP_TRY(hipMemcpy(neg_mu, d_omu.p, sizeof(int) * n_out, hipMemcpyDeviceToHost));
+    NDPP_TRY(hipMemcpy(neg_rows, d_orow.p, 2 * sizeof(int) * n_out, hipMemcpyDeviceToHost));
+    if (neg_min) NDPP_TRY(hipMemcpy(neg_min, d_omin.p, sizeof(double) * n_out, hipMemcpyDeviceToHost));
+    if (neg_mu) NDPP_TRY(hipMemcpy(neg_mu, d_omu.p, sizeof(int) * n_out, hipMemcpyDeviceToHost));
   }
   summary->rows = s.rows;
   summary->negative = s.neg;
@@ -425,21 +411,21 @@ extern "C" int ndpp_expand_moments(int n_ein, int L, const double* moments, int 
     return fail(NDPP_EINVAL, "expand_moments: sizes overflow (n_ein=%d L=%d n_mu=%d)", n_ein, L, n_mu);
   if ((rc = check_mu("expand_moments", n_mu, mu))) return rc;
   if (n_ein == 0) return NDPP_OK;
-  if ((rc = no_device())) return rc;
+  if ((rc = require_device())) return rc;
 
   const std::vector<double> basis = make_basis(n_mu, mu, n_moments);
   const long total = (long)n_ein * n_mu;
   DevBuf<double> d_mom, d_basis, d_out;
-  EXP_TRY(d_mom.upload(moments, (size_t)n_ein * L));
-  EXP_TRY(d_basis.upload(basis.data(), basis.size()));
-  EXP_TRY(d_out.alloc(total));
+  NDPP_TRY(d_mom.upload(moments, (size_t)n_ein * L));
+  NDPP_TRY(d_basis.upload(basis.data(), basis.size()));
+  NDPP_TRY(d_out.alloc(total));
   {
     GpuSpan span(nullptr, -1);
     kExpLaunch[n_moments - 1](total, n_mu, L, d_mom.p, d_basis.p, d_out.p);
     span.end();
-    EXP_TRY(hipGetLastError());
-    EXP_TRY(hipDeviceSynchronize());
+    NDPP_TRY(hipGetLastError());
+    NDPP_TRY(hipDeviceSynchronize());
   }
-  EXP_TRY(hipMemcpy(out, d_out.p, sizeof(double) * total, hipMemcpyDeviceToHost));
+  NDPP_TRY(hipMemcpy(out, d_out.p, sizeof(double) * total, hipMemcpyDeviceToHost));
   return NDPP_OK;
 }

@@ -370,11 +370,10 @@ void launch_file4_any(int n, const int* list, int mu_bins, const double* ein,
                       const double* nuc_awr, const double* nuc_Q) {
   if (n <= 0) return;
   const MuGrid grid = make_mu_grid(mu_bins);
-  if (L <= 4) launch_file4<4>(n, list, grid, ein, row_lo, w_hi, f_tab, awr, Q, G, L, e_bins, rows_per_ein, out, s, nuc_of_ein, nuc_awr, nuc_Q);
-  else if (L <= 6) launch_file4<6>(n, list, grid, ein, row_lo, w_hi, f_tab, awr, Q, G, L, e_bins, rows_per_ein, out, s, nuc_of_ein, nuc_awr, nuc_Q);
-  else if (L <= 8) launch_file4<8>(n, list, grid, ein, row_lo, w_hi, f_tab, awr, Q, G, L, e_bins, rows_per_ein, out, s, nuc_of_ein, nuc_awr, nuc_Q);
-  else launch_file4<11>(n, list, grid, ein, row_lo, w_hi, f_tab, awr, Q, G, L, e_bins, rows_per_ein, out, s, nuc_of_ein, nuc_awr, nuc_Q);
+  dispatch_lmax(L, [&](auto lmax) {
+    launch_file4<decltype(lmax)::value>(n, list, grid, ein, row_lo, w_hi, f_tab, awr, Q, G, L, e_bins, rows_per_ein,
+                                        out, s, nuc_of_ein, nuc_awr, nuc_Q);
+  });
 }
-
 
 }  // namespace ndpp

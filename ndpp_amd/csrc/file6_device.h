@@ -12,6 +12,7 @@
 
 #include "../../include/ndpp_hip.h"
 #include "dev_util.h"
+#include "kernels.h"
 #include "ndpp_math.h"
 
 namespace ndpp {
@@ -505,6 +506,46 @@ __global__ void f6_lab_int_kernel(F6Batch B) {
     B.fEl[t] = live ? acc : 0.0;
     if (k == 0) B.ebnds[(size_t)e * (B.G + 2) + g] = live ? 1.0 : 0.0;
   }
+}
+
+// ---- host: the opening and the closing step of a batch call (the sinks of both translation units) ----
+// Opening: the arrays every bracketed-row call reads -- ein, w_hi, row_lo, the table f_tab[n_f], then
+// (law 9) its edist data, then e_bins -- each in a buffer of its own, uploaded in that order.
+// (One staging upload per call, VERDICT.md item 8, would replace the body of upload().)
+struct BatchInputs {
+  DevBuf<double> ein, w_hi, f_tab, extra, e_bins;
+  DevBuf<int> row_lo;
+  int upload(int n_ein, const double* h_ein, const double* h_w, const int* h_row, size_t n_f, const double* h_f,
+             int G, const double* h_bins, int n_extra = 0, const double* h_extra = nullptr) {
+    NDPP_TRY(ein.upload(h_ein, n_ein));
+    NDPP_TRY(w_hi.upload(h_w, n_ein));
+    NDPP_TRY(row_lo.upload(h_row, n_ein));
+    NDPP_TRY(f_tab.upload(h_f, n_f));
+    if (h_extra) NDPP_TRY(extra.upload(h_extra, n_extra));
+    NDPP_TRY(e_bins.upload(h_bins, G + 1));
+    return NDPP_OK;
+  }
+};
+
+// Closing, after the call's own kernels on the null stream: the status word, the end of the timed
+// span, the launch errors, the sink (which enqueues behind the kernels), ONE synchronise, and the
+// copies to the host (out only without a sink).  Keep the order: the caller's buffers go back to
+// the cache when it returns, so nothing may still be reading them -- every early return is through
+// fail(), which waits, and the sink runs before the synchronise, never after it.
+inline int finish_batch(const double* d_out, int* d_st, int n_ein, size_t GL, int extra_bits, double* out,
+                        int* status, DeviceSink* sink, GpuSpan& span) {
+  hipLaunchKernelGGL(nonfinite_status_kernel, dim3(nblk(n_ein, 64)), dim3(64), 0, 0, n_ein, (int)GL, d_out, d_st,
+                     extra_bits);
+  span.end();
+  NDPP_TRY(hipGetLastError());
+  if (sink) {
+    const int rc = sink->consume(d_out, n_ein, GL);
+    if (rc) return rc;
+  }
+  NDPP_TRY(hipDeviceSynchronize());
+  if (!sink) NDPP_TRY(hipMemcpy(out, d_out, sizeof(double) * n_ein * GL, hipMemcpyDeviceToHost));
+  if (status) NDPP_TRY(hipMemcpy(status, d_st, sizeof(int) * n_ein, hipMemcpyDeviceToHost));
+  return NDPP_OK;
 }
 
 }  // namespace

@@ -234,15 +234,6 @@ __global__ void law9_blend_kernel(int n_ein, const double* w_hi, const double* r
   }
 }
 
-
-
-#define F6_TRY(expr)                                                              \
-  do {                                                                            \
-    hipError_t e_ = (expr);                                                       \
-    if (e_ != hipSuccess)                                                         \
-      return fail(NDPP_EDEVICE, "%s failed: %s", #expr, hipGetErrorString(e_));   \
-  } while (0)
-
 template <int LMAX>
 void launch_cm_point(const F6Batch& B) {
   const long tot = (long)B.n_ein * B.G * B.NEG;
@@ -261,18 +252,6 @@ void launch_law9(int n_ein, const double* ein, const int* row_lo, const MuGrid& 
   const long tot = (long)n_ein * 2 * G;
   hipLaunchKernelGGL((law9_kernel<LMAX>), dim3(nblk(tot, 64)), dim3(64), 0, 0, n_ein, ein,
                      row_lo, grid, f_tab, edata, G, L, e_bins, raw);
-}
-
-int check_common(const ndpp_params* p, int G) {
-  if (!p) return fail(NDPP_EINVAL, "params is NULL");
-  if (p->order < 1 || p->order > NDPP_MAX_ORDER)
-    return fail(NDPP_EINVAL, "order=%d outside 1..%d", p->order, NDPP_MAX_ORDER);
-  if (p->mu_bins < 2) return fail(NDPP_EINVAL, "mu_bins=%d < 2", p->mu_bins);
-  if (G < 1) return fail(NDPP_EINVAL, "need at least one group");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-    return fail(NDPP_EDEVICE, "no HIP device available (libndpp_hip has no CPU path)");
-  return NDPP_OK;
 }
 
 }  // namespace
@@ -318,11 +297,9 @@ int ndpp::file6_batch_sink(const ndpp_params* p, double awr, int frame_cm, int n
     npmax = std::max(npmax, np);
     if (k + 1 < n_rows) ubcap = std::max(ubcap, np + row_ptr[k + 2] - row_ptr[k + 1]);
   }
-  for (int i = 0; i < n_ein; ++i)
-    if (row_lo[i] < 0 || row_lo[i] + 1 >= n_rows)
-      return fail(NDPP_EINVAL, "row_lo[%d]=%d outside [0, n_rows-2]", i, row_lo[i]);
-  int rc = check_common(p, G);
-  if (rc) return rc;
+  int rc;
+  if ((rc = check_row_lo(n_ein, row_lo, n_rows)) || (rc = check_params(p, G, kCheckOrder)) || (rc = require_device()))
+    return rc;
 
   const int L = n_tab > 0 ? n_tab : p->order, M = p->mu_bins, NEG = p->ne_per_grp;
   const size_t ntot = (size_t)row_ptr[n_rows];
@@ -332,37 +309,37 @@ int ndpp::file6_batch_sink(const ndpp_params* p, double awr, int frame_cm, int n
   DevBuf<double> d_ein, d_eg, d_eout, d_pdf, d_f, d_bins, d_uba, d_ubb, d_ub, d_wf, d_Eo, d_pd,
       d_r1, d_r2, d_fEl, d_ebnds, d_out;
   DevBuf<int> d_row, d_rp, d_intt, d_nub, d_j1, d_j2, d_glohi, d_st;
-  F6_TRY(d_ein.upload(ein, n_ein));
-  F6_TRY(d_row.upload(row_lo, n_ein));
-  F6_TRY(d_eg.upload(e_grid, n_rows));
-  F6_TRY(d_rp.upload(row_ptr, n_rows + 1));
-  F6_TRY(d_eout.upload(eout, ntot));
-  F6_TRY(d_pdf.upload(pdf, ntot));
-  F6_TRY(d_intt.upload(intt, n_rows));
-  if (!f_dev) F6_TRY(d_f.upload(f, ntot * M));
-  F6_TRY(d_bins.upload(e_bins, G + 1));
-  F6_TRY(d_uba.alloc((size_t)n_ein * npmax));
-  F6_TRY(d_ubb.alloc((size_t)n_ein * npmax));
-  F6_TRY(d_ub.alloc((size_t)n_ein * ubcap));
-  F6_TRY(d_nub.alloc(n_ein));
-  F6_TRY(d_wf.alloc(n_ein));
-  F6_TRY(d_Eo.alloc((size_t)n_ein * ubcap));
-  F6_TRY(d_pd.alloc((size_t)n_ein * ubcap));
-  F6_TRY(d_j1.alloc((size_t)n_ein * ubcap));
-  F6_TRY(d_j2.alloc((size_t)n_ein * ubcap));
-  F6_TRY(d_r1.alloc((size_t)n_ein * ubcap));
-  F6_TRY(d_r2.alloc((size_t)n_ein * ubcap));
+  NDPP_TRY(d_ein.upload(ein, n_ein));
+  NDPP_TRY(d_row.upload(row_lo, n_ein));
+  NDPP_TRY(d_eg.upload(e_grid, n_rows));
+  NDPP_TRY(d_rp.upload(row_ptr, n_rows + 1));
+  NDPP_TRY(d_eout.upload(eout, ntot));
+  NDPP_TRY(d_pdf.upload(pdf, ntot));
+  NDPP_TRY(d_intt.upload(intt, n_rows));
+  if (!f_dev) NDPP_TRY(d_f.upload(f, ntot * M));
+  NDPP_TRY(d_bins.upload(e_bins, G + 1));
+  NDPP_TRY(d_uba.alloc((size_t)n_ein * npmax));
+  NDPP_TRY(d_ubb.alloc((size_t)n_ein * npmax));
+  NDPP_TRY(d_ub.alloc((size_t)n_ein * ubcap));
+  NDPP_TRY(d_nub.alloc(n_ein));
+  NDPP_TRY(d_wf.alloc(n_ein));
+  NDPP_TRY(d_Eo.alloc((size_t)n_ein * ubcap));
+  NDPP_TRY(d_pd.alloc((size_t)n_ein * ubcap));
+  NDPP_TRY(d_j1.alloc((size_t)n_ein * ubcap));
+  NDPP_TRY(d_j2.alloc((size_t)n_ein * ubcap));
+  NDPP_TRY(d_r1.alloc((size_t)n_ein * ubcap));
+  NDPP_TRY(d_r2.alloc((size_t)n_ein * ubcap));
   const size_t nwork = frame_cm ? (size_t)n_ein * G * NEG * L : (size_t)n_ein * G * M;
-  F6_TRY(d_fEl.alloc(nwork));
-  F6_TRY(d_glohi.alloc((size_t)2 * n_ein));
-  F6_TRY(d_ebnds.alloc((size_t)n_ein * (G + 2)));
-  F6_TRY(d_out.alloc((size_t)n_ein * G * L));
-  F6_TRY(d_st.alloc(n_ein));
+  NDPP_TRY(d_fEl.alloc(nwork));
+  NDPP_TRY(d_glohi.alloc((size_t)2 * n_ein));
+  NDPP_TRY(d_ebnds.alloc((size_t)n_ein * (G + 2)));
+  NDPP_TRY(d_out.alloc((size_t)n_ein * G * L));
+  NDPP_TRY(d_st.alloc(n_ein));
   DevBuf<unsigned> d_list;                       // [items] + the count behind them
   const size_t n_items = frame_cm ? (size_t)n_ein * G * NEG : 0;
   if (n_items >= 0xffffffffull) return fail(NDPP_EINVAL, "file 6 CM batch of %zu items: split the call", n_items);
-  F6_TRY(d_list.alloc(n_items + 1));
-  F6_TRY(hipMemsetAsync(d_list.p + n_items, 0, sizeof(unsigned), 0));
+  NDPP_TRY(d_list.alloc(n_items + 1));
+  NDPP_TRY(hipMemsetAsync(d_list.p + n_items, 0, sizeof(unsigned), 0));
   B.cm_list = d_list.p; B.cm_live = d_list.p + n_items;
   B.ein = d_ein.p; B.row_lo = d_row.p; B.e_grid = d_eg.p; B.row_ptr = d_rp.p;
   B.eout = d_eout.p; B.pdf = d_pdf.p; B.intt = d_intt.p; B.f = f_dev ? f_dev : d_f.p; B.e_bins = d_bins.p;
@@ -378,90 +355,59 @@ int ndpp::file6_batch_sink(const ndpp_params* p, double awr, int frame_cm, int n
     launch_f6_tab(B);
   } else if (frame_cm) {
     hipLaunchKernelGGL(f6_cm_bounds_kernel, dim3(nblk(n_ein, 64)), dim3(64), 0, 0, B);
-    if (L <= 4) launch_cm_point<4>(B);
-    else if (L <= 6) launch_cm_point<6>(B);
-    else if (L <= 8) launch_cm_point<8>(B);
-    else launch_cm_point<11>(B);
+    dispatch_lmax(L, [&](auto lmax) { launch_cm_point<decltype(lmax)::value>(B); });
     hipLaunchKernelGGL(f6_cm_finish_kernel, dim3(nblk(n_ein, 64)), dim3(64), 0, 0, B);
   } else {
     hipLaunchKernelGGL(f6_lab_int_kernel, dim3(nblk((long)n_ein * G * M, 256)), dim3(256), 0, 0, B);
-    if (L <= 4) launch_lab_panel<4>(B);
-    else if (L <= 6) launch_lab_panel<6>(B);
-    else if (L <= 8) launch_lab_panel<8>(B);
-    else launch_lab_panel<11>(B);
+    dispatch_lmax(L, [&](auto lmax) { launch_lab_panel<decltype(lmax)::value>(B); });
     hipLaunchKernelGGL(f6_lab_norm_kernel, dim3(nblk(n_ein, 64)), dim3(64), 0, 0, B);
   }
-  hipLaunchKernelGGL(nonfinite_status_kernel, dim3(nblk(n_ein, 64)), dim3(64), 0, 0, n_ein, G * L, d_out.p, d_st.p,
-                     order_noise_bits(L));
-  span.end();
-  F6_TRY(hipGetLastError());
-  if (sink) {
-    rc = sink->consume(d_out.p, n_ein, (size_t)G * L);
-    if (rc) return rc;
-  }
-  F6_TRY(hipDeviceSynchronize());
-  if (!sink) F6_TRY(hipMemcpy(out, d_out.p, sizeof(double) * (size_t)n_ein * G * L, hipMemcpyDeviceToHost));
-  if (status) F6_TRY(hipMemcpy(status, d_st.p, sizeof(int) * n_ein, hipMemcpyDeviceToHost));
-  return NDPP_OK;
+  return finish_batch(d_out.p, d_st.p, n_ein, (size_t)G * L, order_noise_bits(L), out, status, sink, span);
 }
 
 extern "C" int ndpp_law9_leg_batch(const ndpp_params* p, int n_ein, const double* ein,
                                    const int* row_lo, const double* w_hi, int n_rows,
                                    const double* f_tab, int n_edata, const double* edata, int G,
                                    const double* e_bins, double* out, int* status) {
-  return law9_leg_batch_sink(p, n_ein, ein, row_lo, w_hi, n_rows, f_tab, n_edata, edata, G, e_bins, out,
-                             status, nullptr);
+  return law9_batch_sink(p, n_ein, ein, row_lo, w_hi, n_rows, f_tab, n_edata, edata, G, e_bins, 0, out, status,
+                         nullptr);
 }
 
-int ndpp::law9_leg_batch_sink(const ndpp_params* p, int n_ein, const double* ein,
-                              const int* row_lo, const double* w_hi, int n_rows,
-                              const double* f_tab, int n_edata, const double* edata, int G,
-                              const double* e_bins, double* out, int* status, DeviceSink* sink) {
+// n_tab = 0: the Legendre moments; n_tab > 0: the tabular bins (law9_tab_kernel, tab_kernels.hip) --
+// everything but the integrating kernel is shared.  The tabular call checks its parameters first and
+// does not read the order; the Legendre call checks them last (n_ein = 0 is an empty call whatever
+// they are): as the two entry points always did.
+int ndpp::law9_batch_sink(const ndpp_params* p, int n_ein, const double* ein, const int* row_lo,
+                          const double* w_hi, int n_rows, const double* f_tab, int n_edata,
+                          const double* edata, int G, const double* e_bins, int n_tab, double* out,
+                          int* status, DeviceSink* sink) {
+  int rc;
+  if (n_tab != 0 && (rc = check_params(p, G, kCheckTab, n_tab))) return rc;
   if (n_ein < 0 || n_rows < 2 || n_edata < 5) return fail(NDPP_EINVAL, "bad sizes");
   if (n_ein == 0) return NDPP_OK;
   if (!p || !ein || !row_lo || !w_hi || !f_tab || !edata || !e_bins || (!out && !sink))
     return fail(NDPP_EINVAL, "NULL argument");
-  for (int i = 0; i < n_ein; ++i)
-    if (row_lo[i] < 0 || row_lo[i] + 1 >= n_rows)
-      return fail(NDPP_EINVAL, "row_lo[%d]=%d outside [0, n_rows-2]", i, row_lo[i]);
-  {
-    const int NR = (int)edata[0];
-    if (NR < 0 || 2 + 2 * NR > n_edata) return fail(NDPP_EINVAL, "edata: bad NR");
-    const int NE = (int)edata[1 + 2 * NR];
-    if (NE < 1 || 2 + 2 * NR + 2 * NE + 1 > n_edata) return fail(NDPP_EINVAL, "edata: bad NE");
-  }
-  int rc = check_common(p, G);
-  if (rc) return rc;
-  const int L = p->order, M = p->mu_bins, GL = G * L;
-  DevBuf<double> d_ein, d_w, d_f, d_ed, d_bins, d_raw, d_out;
-  DevBuf<int> d_row, d_st;
-  F6_TRY(d_ein.upload(ein, n_ein));
-  F6_TRY(d_w.upload(w_hi, n_ein));
-  F6_TRY(d_row.upload(row_lo, n_ein));
-  F6_TRY(d_f.upload(f_tab, (size_t)n_rows * M));
-  F6_TRY(d_ed.upload(edata, n_edata));
-  F6_TRY(d_bins.upload(e_bins, G + 1));
-  F6_TRY(d_raw.alloc((size_t)n_ein * 2 * GL));
-  F6_TRY(d_out.alloc((size_t)n_ein * GL));
-  F6_TRY(d_st.alloc(n_ein));
-  const MuGrid grid = make_mu_grid(M);
+  if ((rc = check_row_lo(n_ein, row_lo, n_rows)) || (rc = check_law9_edata(n_edata, edata))) return rc;
+  if (n_tab == 0 && (rc = check_params(p, G, kCheckOrder))) return rc;
+  if ((rc = require_device())) return rc;
+  const int L = n_tab > 0 ? n_tab : p->order, M = p->mu_bins, GL = G * L;
+  BatchInputs in;
+  if ((rc = in.upload(n_ein, ein, w_hi, row_lo, (size_t)n_rows * M, f_tab, G, e_bins, n_edata, edata))) return rc;
+  DevBuf<double> d_raw, d_out;
+  DevBuf<int> d_st;
+  NDPP_TRY(d_raw.alloc((size_t)n_ein * 2 * GL));
+  NDPP_TRY(d_out.alloc((size_t)n_ein * GL));
+  NDPP_TRY(d_st.alloc(n_ein));
   GpuSpan span(nullptr, kProfLaw9);
-  if (L <= 4) launch_law9<4>(n_ein, d_ein.p, d_row.p, grid, d_f.p, d_ed.p, G, L, d_bins.p, d_raw.p);
-  else if (L <= 6) launch_law9<6>(n_ein, d_ein.p, d_row.p, grid, d_f.p, d_ed.p, G, L, d_bins.p, d_raw.p);
-  else if (L <= 8) launch_law9<8>(n_ein, d_ein.p, d_row.p, grid, d_f.p, d_ed.p, G, L, d_bins.p, d_raw.p);
-  else launch_law9<11>(n_ein, d_ein.p, d_row.p, grid, d_f.p, d_ed.p, G, L, d_bins.p, d_raw.p);
+  if (n_tab > 0)
+    launch_law9_tab(n_ein, in.ein.p, in.row_lo.p, M, in.f_tab.p, in.extra.p, G, L, in.e_bins.p, d_raw.p);
+  else
+    dispatch_lmax(L, [&](auto lmax) {
+      launch_law9<decltype(lmax)::value>(n_ein, in.ein.p, in.row_lo.p, make_mu_grid(M), in.f_tab.p, in.extra.p, G,
+                                         L, in.e_bins.p, d_raw.p);
+    });
   hipLaunchKernelGGL(law9_blend_kernel, dim3(nblk((long)n_ein * GL, 256)), dim3(256), 0, 0, n_ein,
-                     d_w.p, d_raw.p, GL, d_out.p, d_st.p);
-  hipLaunchKernelGGL(nonfinite_status_kernel, dim3(nblk(n_ein, 64)), dim3(64), 0, 0, n_ein, GL, d_out.p, d_st.p,
-                     order_noise_bits(L));
-  span.end();
-  F6_TRY(hipGetLastError());
-  if (sink) {
-    rc = sink->consume(d_out.p, n_ein, (size_t)GL);
-    if (rc) return rc;
-  }
-  F6_TRY(hipDeviceSynchronize());
-  if (!sink) F6_TRY(hipMemcpy(out, d_out.p, sizeof(double) * (size_t)n_ein * GL, hipMemcpyDeviceToHost));
-  if (status) F6_TRY(hipMemcpy(status, d_st.p, sizeof(int) * n_ein, hipMemcpyDeviceToHost));
-  return NDPP_OK;
+                     in.w_hi.p, d_raw.p, GL, d_out.p, d_st.p);
+  return finish_batch(d_out.p, d_st.p, n_ein, (size_t)GL, n_tab > 0 ? 0 : order_noise_bits(L), out, status, sink,
+                      span);
 }

@@ -66,13 +66,6 @@ grid_error_kernel(int n_int, int GL, int L, const double* __restrict__ y, const 
   }
 }
 
-#define GRID_TRY(expr)                                                            \
-  do {                                                                            \
-    hipError_t e_ = (expr);                                                       \
-    if (e_ != hipSuccess)                                                         \
-      return fail(NDPP_EDEVICE, "%s failed: %s", #expr, hipGetErrorString(e_));   \
-  } while (0)
-
 }  // namespace
 }  // namespace ndpp
 
@@ -84,9 +77,7 @@ extern "C" int ndpp_grid_error(int L, int G, int n, const double* x, const doubl
   if (!x || !y || !x_mid || !y_mid || !err || !arg) return fail(NDPP_EINVAL, "grid_error: NULL argument");
   if ((long)G * L > INT_MAX / 2) return fail(NDPP_EINVAL, "grid_error: G * L = %ld does not fit an index", (long)G * L);
   const int GL = G * L, n_int = n - 1;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-    return fail(NDPP_EDEVICE, "no HIP device available (libndpp_hip has no CPU path)");
+  if (int rc = require_device()) return rc;
 
   // f per interval; -1 marks the intervals that are skipped: abscissae that are not positive and
   // finite, x[i+1] <= x[i], or x_mid outside (x[i], x[i+1])
@@ -98,20 +89,20 @@ extern "C" int ndpp_grid_error(int L, int G, int n, const double* x, const doubl
   }
   DevBuf<double> d_y, d_mid, d_f, d_err;
   DevBuf<int> d_arg;
-  GRID_TRY(d_y.upload(y, (size_t)n * GL));
-  GRID_TRY(d_mid.upload(y_mid, (size_t)n_int * GL));
-  GRID_TRY(d_f.upload(f.data(), f.size()));
-  GRID_TRY(d_err.alloc(n_int));
-  GRID_TRY(d_arg.alloc(n_int));
+  NDPP_TRY(d_y.upload(y, (size_t)n * GL));
+  NDPP_TRY(d_mid.upload(y_mid, (size_t)n_int * GL));
+  NDPP_TRY(d_f.upload(f.data(), f.size()));
+  NDPP_TRY(d_err.alloc(n_int));
+  NDPP_TRY(d_arg.alloc(n_int));
   {
     GpuSpan span(nullptr, -1);
     hipLaunchKernelGGL(grid_error_kernel, dim3(nblk((long)n_int * 64, kThreads)), dim3(kThreads), 0, 0, n_int, GL, L,
                        d_y.p, d_mid.p, d_f.p, d_err.p, d_arg.p);
     span.end();
-    GRID_TRY(hipGetLastError());
-    GRID_TRY(hipDeviceSynchronize());
+    NDPP_TRY(hipGetLastError());
+    NDPP_TRY(hipDeviceSynchronize());
   }
-  GRID_TRY(hipMemcpy(err, d_err.p, sizeof(double) * n_int, hipMemcpyDeviceToHost));
-  GRID_TRY(hipMemcpy(arg, d_arg.p, sizeof(int) * n_int, hipMemcpyDeviceToHost));
+  NDPP_TRY(hipMemcpy(err, d_err.p, sizeof(double) * n_int, hipMemcpyDeviceToHost));
+  NDPP_TRY(hipMemcpy(arg, d_arg.p, sizeof(int) * n_int, hipMemcpyDeviceToHost));
   return NDPP_OK;
 }

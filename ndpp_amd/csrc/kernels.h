@@ -2,12 +2,47 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "../../include/ndpp_hip.h"
 
 namespace ndpp {
 
 // records the message returned by ndpp_last_error() and returns `code`
 int fail(int code, const char* fmt, ...);
+
+// a HIP call of a function that returns an NDPP code: its failure is NDPP_EDEVICE, through fail()
+#define NDPP_TRY(expr)                                                        \
+  do {                                                                        \
+    hipError_t e_ = (expr);                                                   \
+    if (e_ != hipSuccess)                                                     \
+      return fail(NDPP_EDEVICE, "%s failed: %s (%s:%d)", #expr,               \
+                  hipGetErrorString(e_), __FILE__, __LINE__);                 \
+  } while (0)
+
+// ---- the host checks the batch entry points share (ndpp_hip.hip); each returns NDPP_OK or what
+// fail() returned.  An entry point calls require_device LAST: a bad argument is reported before a
+// missing device is.
+// NDPP_EDEVICE when there is no device ("<who>: " in front of the message if given)
+int require_device(const char* who = nullptr);
+// every row_lo[i] has a row above it: 0 <= row_lo[i] <= n_rows - 2
+int check_row_lo(int n_ein, const int* row_lo, int n_rows);
+// the law-9 edist%data [NR, (NBT, INT) x NR, NE, E(NE), T(NE), U] fits its n_edata words
+int check_law9_edata(int n_edata, const double* edata);
+// params non-null, mu_bins >= 2 and G >= 1, and what `what` adds: the order (Legendre output), n_tab
+// (tabular output, which does not read the order), the adaptive limits and tolerances (free gas)
+enum ParamChecks { kCheckOrder = 1, kCheckTab = 2, kCheckFreegas = 4 };
+int check_params(const ndpp_params* p, int G, int what, int n_tab = 0);
+
+// f(std::integral_constant<int, LMAX>) with the smallest LMAX of 4, 6, 8, 11 that holds L orders:
+// the kernels that keep their moments in registers are instantiated for these four
+template <class F>
+auto dispatch_lmax(int L, F&& f) {
+  if (L <= 4) return f(std::integral_constant<int, 4>());
+  if (L <= 6) return f(std::integral_constant<int, 6>());
+  if (L <= 8) return f(std::integral_constant<int, 8>());
+  return f(std::integral_constant<int, 11>());
+}
 
 // hipEvent bracket around the kernels of one batch call: the span between
 // construction and end() is what ndpp_last_gpu_ms() reports (uploads, downloads
@@ -78,19 +113,19 @@ int file6_batch_sink(const ndpp_params* p, double awr, int frame_cm, int n_ein, 
                      const double* eout, const double* pdf, const int* intt, const double* f, int G,
                      const double* e_bins, int n_tab, double* out, int* status, DeviceSink* sink,
                      const double* f_dev = nullptr);
-int law9_leg_batch_sink(const ndpp_params* p, int n_ein, const double* ein, const int* row_lo,
-                        const double* w_hi, int n_rows, const double* f_tab, int n_edata,
-                        const double* edata, int G, const double* e_bins, double* out, int* status,
-                        DeviceSink* sink);
-// tab_kernels.hip: the tabular counterparts of elastic_leg_batch_sink and law9_leg_batch_sink
+// n_tab = 0: the Legendre moments of ndpp_law9_leg_batch; n_tab > 0: the bins of ndpp_law9_tab_batch
+int law9_batch_sink(const ndpp_params* p, int n_ein, const double* ein, const int* row_lo,
+                    const double* w_hi, int n_rows, const double* f_tab, int n_edata,
+                    const double* edata, int G, const double* e_bins, int n_tab, double* out, int* status,
+                    DeviceSink* sink);
+// tab_kernels.hip: law9_batch_sink's integrating kernel for n_tab = N > 0 (raw [n_ein][2][G][N], null
+// stream), and the tabular counterpart of elastic_leg_batch_sink
+void launch_law9_tab(int n_ein, const double* ein, const int* row_lo, int mu_bins, const double* f_tab,
+                     const double* edata, int G, int N, const double* e_bins, double* raw);
 int elastic_tab_batch_sink(const ndpp_params* p, double A, double kT, double freegas_cutoff, double Q,
                            int n_ein, const double* ein, const int* row_lo, const double* w_hi,
                            int n_rows, const double* f_tab, int G, const double* e_bins, int n_tab,
                            double* out, int* status, DeviceSink* sink);
-int law9_tab_batch_sink(const ndpp_params* p, int n_ein, const double* ein, const int* row_lo,
-                        const double* w_hi, int n_rows, const double* f_tab, int n_edata,
-                        const double* edata, int G, const double* e_bins, int n_tab, double* out,
-                        int* status, DeviceSink* sink);
 // P0 of one group's row of L entries: the first moment, or (tab) the sum of the bins
 inline double group_p0(const double* m, int L, bool tab) {
   if (!tab) return m[0];

@@ -350,14 +350,6 @@ extern "C" float ndpp_last_gpu_ms(void) { return ndpp::g_last_gpu_ms; }
 
 namespace {
 
-#define HIP_TRY(expr)                                                         \
-  do {                                                                        \
-    hipError_t e_ = (expr);                                                   \
-    if (e_ != hipSuccess)                                                     \
-      return fail(NDPP_EDEVICE, "%s failed: %s (%s:%d)", #expr,               \
-                  hipGetErrorString(e_), __FILE__, __LINE__);                 \
-  } while (0)
-
 // Cached workspace, one per device, each with its own lock: batch calls on one device are
 // serialised (they share the arena), calls on different devices -- host threads that each
 // selected their own GPU -- run concurrently and keep their arenas.
@@ -372,15 +364,10 @@ struct Workspace {
 constexpr int kMaxDevices = 64;
 Workspace g_ws_of[kMaxDevices];
 
-int require_device() {
-  if (ndpp_device_count() > 0) return NDPP_OK;
-  return fail(NDPP_EDEVICE, "no HIP device available (libndpp_hip has no CPU path)");
-}
-
 // the calling thread's current device and its workspace
 int current_workspace(Workspace** ws) {
   int dev = 0;
-  HIP_TRY(hipGetDevice(&dev));
+  NDPP_TRY(hipGetDevice(&dev));
   if (dev < 0 || dev >= kMaxDevices) return fail(NDPP_EDEVICE, "device ordinal %d outside 0..%d", dev, kMaxDevices - 1);
   *ws = &g_ws_of[dev];
   return NDPP_OK;
@@ -419,12 +406,39 @@ struct Carver {
   }
 };
 
-int check_params(const ndpp_params* p, int G) {
+}  // namespace
+
+// ---- the host checks every batch entry point shares (kernels.h) ----
+int ndpp::require_device(const char* who) {
+  if (ndpp_device_count() > 0) return NDPP_OK;
+  return fail(NDPP_EDEVICE, "%s%sno HIP device available (libndpp_hip has no CPU path)", who ? who : "",
+              who ? ": " : "");
+}
+
+int ndpp::check_row_lo(int n_ein, const int* row_lo, int n_rows) {
+  for (int i = 0; i < n_ein; ++i)
+    if (row_lo[i] < 0 || row_lo[i] + 1 >= n_rows)
+      return fail(NDPP_EINVAL, "row_lo[%d]=%d outside [0, n_rows-2]", i, row_lo[i]);
+  return NDPP_OK;
+}
+
+int ndpp::check_law9_edata(int n_edata, const double* edata) {
+  const int NR = (int)edata[0];
+  if (NR < 0 || 2 + 2 * NR > n_edata) return fail(NDPP_EINVAL, "edata: bad NR");
+  const int NE = (int)edata[1 + 2 * NR];
+  if (NE < 1 || 2 + 2 * NR + 2 * NE + 1 > n_edata) return fail(NDPP_EINVAL, "edata: bad NE");
+  return NDPP_OK;
+}
+
+int ndpp::check_params(const ndpp_params* p, int G, int what, int n_tab) {
   if (!p) return fail(NDPP_EINVAL, "params is NULL");
-  if (p->order < 1 || p->order > NDPP_MAX_ORDER)
+  if ((what & kCheckOrder) && (p->order < 1 || p->order > NDPP_MAX_ORDER))
     return fail(NDPP_EINVAL, "order=%d outside 1..%d", p->order, NDPP_MAX_ORDER);
+  if ((what & kCheckTab) && (n_tab < 1 || n_tab > NDPP_MAX_TAB_BINS))
+    return fail(NDPP_EINVAL, "n_tab=%d outside 1..%d", n_tab, NDPP_MAX_TAB_BINS);
   if (p->mu_bins < 2) return fail(NDPP_EINVAL, "mu_bins=%d < 2", p->mu_bins);
   if (G < 1) return fail(NDPP_EINVAL, "need at least one group");
+  if (!(what & kCheckFreegas)) return NDPP_OK;
   if (p->adaptive_mu_its < 0 || p->adaptive_mu_its >= kMaxLevels ||
       p->adaptive_eout_its < 0 || p->adaptive_eout_its >= kMaxLevels)
     return fail(NDPP_EINVAL, "adaptive_*_its must be in 0..%d", kMaxLevels - 1);
@@ -436,6 +450,11 @@ int check_params(const ndpp_params* p, int G) {
       return fail(NDPP_EINVAL, "tolerances (sab_threshold, brent_mu_thresh, adaptive_*_tol) must be finite and >= 0");
   return NDPP_OK;
 }
+
+namespace {
+
+// the free-gas view of check_params: the order and everything the adaptive integration reads
+int check_params(const ndpp_params* p, int G) { return ndpp::check_params(p, G, kCheckOrder | kCheckFreegas); }
 
 inline int gs_blocks(long n, int threads = 256) {
   return (int)std::max<long>(1, std::min<long>((n + threads - 1) / threads, 4096));
@@ -611,8 +630,8 @@ int plan_batch(const ndpp_params* p, int n_ein, int n_rows, int G, int rows_per_
   if (g_ws.num_cu == 0) {
     hipDeviceProp_t prop;
     int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    HIP_TRY(hipGetDeviceProperties(&prop, dev));
+    NDPP_TRY(hipGetDevice(&dev));
+    NDPP_TRY(hipGetDeviceProperties(&prop, dev));
     g_ws.num_cu = prop.multiProcessorCount;
   }
   pl.num_cu = g_ws.num_cu;
@@ -653,7 +672,7 @@ int plan_batch(const ndpp_params* p, int n_ein, int n_rows, int G, int rows_per_
     budget = g_ws.bytes;
     free_b = g_ws.bytes;
   } else {
-    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+    NDPP_TRY(hipMemGetInfo(&free_b, &total_b));
     if (g_ws.base) free_b += g_ws.bytes;
     budget = std::min<size_t>((size_t)(free_b * 0.6), (size_t)128 << 30);
   }
@@ -755,8 +774,8 @@ hipError_t upload_mask_rank(int* dst, int nb, hipStream_t stream) {
 // energies into the three lists of the head.  Waits for the device: the list lengths decide what follows.
 int classify_batch(const BatchCall& a, const FgTunables& t, bool look_at_tables, BatchHead& h) {
   hipStream_t stream = a.stream;
-  HIP_TRY(hipMemsetAsync(h.counters, 0, 64 * sizeof(int), stream));
-  HIP_TRY(hipMemsetAsync(h.dstats, 0, kNumStats * sizeof(unsigned long long), stream));
+  NDPP_TRY(hipMemsetAsync(h.counters, 0, 64 * sizeof(int), stream));
+  NDPP_TRY(hipMemsetAsync(h.dstats, 0, kNumStats * sizeof(unsigned long long), stream));
   const dim3 grid(gs_blocks(a.n_ein)), block(256);
   hipLaunchKernelGGL(check_rows_kernel, grid, block, 0, stream, a.n_ein, a.row_lo, a.n_rows, a.rows_per_ein,
                      h.counters + 3);
@@ -771,8 +790,8 @@ int classify_batch(const BatchCall& a, const FgTunables& t, bool look_at_tables,
                      t.strict_x, t.strict_cold, a.A, a.kT, a.nuc.A, a.nuc.kT, h.fgs_list, h.counters + 5,
                      look_at_tables ? h.rough : nullptr, a.row_lo, a.rows_per_ein, a.n_rows);
   int hc[6];
-  HIP_TRY(hipMemcpyAsync(hc, h.counters, sizeof(hc), hipMemcpyDeviceToHost, stream));
-  HIP_TRY(hipStreamSynchronize(stream));
+  NDPP_TRY(hipMemcpyAsync(hc, h.counters, sizeof(hc), hipMemcpyDeviceToHost, stream));
+  NDPP_TRY(hipStreamSynchronize(stream));
   if (hc[3]) return fail(NDPP_EINVAL, "row_lo outside [0, n_rows-%d]", a.rows_per_ein);
   if (hc[4]) return fail(NDPP_EINVAL, "nuc_of_ein outside [0, n_nuc)");
   h.n_fast = hc[0], h.n_f4 = hc[1], h.n_strict = hc[5];
@@ -854,7 +873,7 @@ int carve_contexts(std::vector<FgCtx>& ctx, bool side_by_side, const BatchCall& 
                    const BatchPlan& pl, const BatchHead& h, Carver cv, bool gauss_on, Workspace& ws) {
   const int nctx = (int)ctx.size(), ncap = (int)pl.ncap, L = a.p->order;
   for (int k = 1; side_by_side && k < nctx; ++k)
-    if (!ws.aux[k - 1]) HIP_TRY(hipStreamCreateWithFlags(&ws.aux[k - 1], hipStreamNonBlocking));
+    if (!ws.aux[k - 1]) NDPP_TRY(hipStreamCreateWithFlags(&ws.aux[k - 1], hipStreamNonBlocking));
   FgBatch T;
   T.gl_ratio = t.gl_ratio; T.gl_near = t.gl_near; T.gl_amin = t.gl_amin; T.gl_cert_depth = t.gl_cert_depth;
   T.gl_cert_depth_near = t.gl_cert_depth_near; T.gl_graded = t.gl_graded; T.gl_panels = t.gl_panels;
@@ -1005,9 +1024,9 @@ int enqueue_chunk(FgCtx& c, const BatchCall& a, const FgTunables& t, const Batch
     c.chunk_ein = std::max<long>(1, c.chunk_ein / 2);
   }
   const int* lst = c.list + (size_t)c.done * c.lstride;
-  HIP_TRY(hipMemsetAsync(c.sl.lvl_cnt, 0, (kMaxLevels + 2) * sizeof(int), s));
-  HIP_TRY(hipMemsetAsync(c.sl.next_task, 0, 2 * (kMaxLevels + 2) * sizeof(int), s));
-  HIP_TRY(hipMemsetAsync(c.sl.overflow, 0, sizeof(int), s));
+  NDPP_TRY(hipMemsetAsync(c.sl.lvl_cnt, 0, (kMaxLevels + 2) * sizeof(int), s));
+  NDPP_TRY(hipMemsetAsync(c.sl.next_task, 0, 2 * (kMaxLevels + 2) * sizeof(int), s));
+  NDPP_TRY(hipMemsetAsync(c.sl.overflow, 0, sizeof(int), s));
   hipLaunchKernelGGL(fg_set_int_kernel, dim3(1), dim3(1), 0, s, c.sl.lvl_cnt, B.n_trees());
   hipLaunchKernelGGL(make_jobs_kernel, dim3(gs_blocks(B.n_jobs)), dim3(256), 0, s, B.n_jobs, rows_per_ein, pl.joint,
                      lst, c.lstride, a.ein, a.row_lo, c.job_ein, c.job_row, a.nuc.nuc_of_ein, a.nuc.A, a.nuc.kT,
@@ -1023,15 +1042,15 @@ int enqueue_chunk(FgCtx& c, const BatchCall& a, const FgTunables& t, const Batch
     if (int rc = fg_strict_stages().prep(&B, sizeof B, level, s)) return rc;
     if (B.t_gl) {
       c.gauss_ev.emplace_back();
-      HIP_TRY(c.gauss_ev.back().before.record(s));
+      NDPP_TRY(c.gauss_ev.back().before.record(s));
       launch_gauss_any(B, level, pl.num_cu, t.gauss_phased, s);
-      HIP_TRY(c.gauss_ev.back().after.record(s));
+      NDPP_TRY(c.gauss_ev.back().after.record(s));
     }
     if (t.sort) {
       // nodes sorted by weight class and the orders still active in any row; nodes with nothing
       // left for the walk last (fg_node_bucket)
       B.mu_nodes = c.sl.mu_nodes;
-      HIP_TRY(hipMemsetAsync(c.sl.mask_hist, 0, sizeof(int) * pl.nb_sort, s));
+      NDPP_TRY(hipMemsetAsync(c.sl.mask_hist, 0, sizeof(int) * pl.nb_sort, s));
       hipLaunchKernelGGL(fg_sort_count_kernel, dim3(1024), dim3(256), 0, s, B, level, pl.nb_sort, c.sl.mask_hist);
       hipLaunchKernelGGL(fg_sort_scan_kernel, dim3(1), dim3(256), 0, s, c.sl.mask_hist, pl.nb_sort, c.sl.mu_nodes);
       hipLaunchKernelGGL(fg_sort_scatter_kernel, dim3(1024), dim3(256), 0, s, B, level, pl.nb_sort,
@@ -1040,9 +1059,9 @@ int enqueue_chunk(FgCtx& c, const BatchCall& a, const FgTunables& t, const Batch
     if (B.seg)
       if (int rc = st.seg_zero(&B, sizeof B, level, s)) return rc;
     c.walk_ev.emplace_back();
-    HIP_TRY(c.walk_ev.back().before.record(s));
+    NDPP_TRY(c.walk_ev.back().before.record(s));
     if (int rc = st.mu(&B, sizeof B, level, pl.num_cu, c.sl.gstack, c.sl.next_task + level, s)) return rc;
-    HIP_TRY(c.walk_ev.back().after.record(s));
+    NDPP_TRY(c.walk_ev.back().after.record(s));
     if (int rc = st.combine(&B, sizeof B, level, s)) return rc;
     B.mu_nodes = nullptr;
     if (int rc = st.node(&B, sizeof B, level, s)) return rc;
@@ -1064,9 +1083,9 @@ int enqueue_chunk(FgCtx& c, const BatchCall& a, const FgTunables& t, const Batch
 int retire_chunk(FgCtx& c, FgTiming& tm) {
   c.inflight = false;
   int ovf = 0;
-  HIP_TRY(hipMemcpyAsync(&ovf, c.sl.overflow, sizeof(int), hipMemcpyDeviceToHost, c.sl.s));
-  HIP_TRY(hipStreamSynchronize(c.sl.s));
-  HIP_TRY(hipGetLastError());
+  NDPP_TRY(hipMemcpyAsync(&ovf, c.sl.overflow, sizeof(int), hipMemcpyDeviceToHost, c.sl.s));
+  NDPP_TRY(hipStreamSynchronize(c.sl.s));
+  NDPP_TRY(hipGetLastError());
   tm.fold(c.walk_ev, true);
   tm.fold(c.gauss_ev, false);
   if (ovf) {
@@ -1153,13 +1172,13 @@ int run_batch_d(const ndpp_params* p, double A, double kT, double cutoff, double
   const bool gauss_on = NDPP_FAST && look_at_tables && t.gauss &&
                         fg_gauss_box(p->adaptive_mu_its, p->adaptive_mu_tol);
   FgTiming tm;
-  HIP_TRY(upload_mask_rank(h.mask_rank, 1 << p->order, stream));
-  HIP_TRY(tm.ev0.record(stream));
+  NDPP_TRY(upload_mask_rank(h.mask_rank, 1 << p->order, stream));
+  NDPP_TRY(tm.ev0.record(stream));
   if ((rc = classify_batch(a, t, look_at_tables, h))) return rc;
   // ---- file4-CM part ------------------------------------------------------
   launch_file4_any(h.n_f4, h.f4_list, p->mu_bins, ein_d, row_lo_d, w_hi_d, f_tab_d, A, Q, G, p->order, e_bins_d,
                    rows_per_ein, out_d, stream, a.nuc.nuc_of_ein, a.nuc.A, a.nuc.Q);
-  HIP_TRY(tm.ev_f4.record(stream));
+  NDPP_TRY(tm.ev_f4.record(stream));
   // ---- free-gas part (FgCtx) ------------------------------------------------
   bool side_by_side = false;
   std::vector<FgCtx> ctx = deal_contexts(h, t, pl, side_by_side);
@@ -1171,11 +1190,11 @@ int run_batch_d(const ndpp_params* p, double A, double kT, double cutoff, double
   if (status_d)
     hipLaunchKernelGGL(status_kernel, dim3(gs_blocks(n_ein)), dim3(256), 0, stream, n_ein, ein_d, out_d, a.GL(),
                        row_lo_d, n_rows, rows_per_ein, status_d);
-  HIP_TRY(tm.ev1.record(stream));
+  NDPP_TRY(tm.ev1.record(stream));
   unsigned long long hs[kNumStats];
-  HIP_TRY(hipMemcpyAsync(hs, h.dstats, sizeof(hs), hipMemcpyDeviceToHost, stream));
-  HIP_TRY(hipStreamSynchronize(stream));
-  HIP_TRY(hipGetLastError());
+  NDPP_TRY(hipMemcpyAsync(hs, h.dstats, sizeof(hs), hipMemcpyDeviceToHost, stream));
+  NDPP_TRY(hipStreamSynchronize(stream));
+  NDPP_TRY(hipGetLastError());
   tm.publish(hs, side_by_side ? nctx : 1, stats);
   return NDPP_OK;
 }
@@ -1198,24 +1217,24 @@ int run_batch_h(const ndpp_params* p, double A, double kT, double cutoff, double
   // (every error below returns through fail(), which waits for the device before these go back to the cache)
   DevBuf<double> ein_d, w_d, f_d, eb_d, out_d;
   DevBuf<int> row_d, st_d;
-  HIP_TRY(ein_d.upload(ein, n_ein));
-  HIP_TRY(w_d.upload(w_hi, n_ein));              // (no w_hi: allocated only)
-  HIP_TRY(row_d.upload(row_lo, n_ein));
-  HIP_TRY(st_d.alloc(n_ein));
-  HIP_TRY(f_d.upload(f_tab, (size_t)n_rows * M));
-  HIP_TRY(eb_d.upload(e_bins, G + 1));
-  HIP_TRY(out_d.alloc(n_ein * GL));
+  NDPP_TRY(ein_d.upload(ein, n_ein));
+  NDPP_TRY(w_d.upload(w_hi, n_ein));              // (no w_hi: allocated only)
+  NDPP_TRY(row_d.upload(row_lo, n_ein));
+  NDPP_TRY(st_d.alloc(n_ein));
+  NDPP_TRY(f_d.upload(f_tab, (size_t)n_rows * M));
+  NDPP_TRY(eb_d.upload(e_bins, G + 1));
+  NDPP_TRY(out_d.alloc(n_ein * GL));
   rc = run_batch_d(p, A, kT, cutoff, Q, n_ein, ein_d.p, row_d.p, w_d.p, n_rows, f_d.p, G, eb_d.p,
                    out_d.p, st_d.p, rows_per_ein, nullptr, stats);
   if (rc) return rc;
   if (sink) {
     rc = sink->consume(out_d.p, n_ein, GL);
     if (rc) return rc;
-    HIP_TRY(hipDeviceSynchronize());
+    NDPP_TRY(hipDeviceSynchronize());
   } else {
-    HIP_TRY(out_d.download(out, n_ein * GL));
+    NDPP_TRY(out_d.download(out, n_ein * GL));
   }
-  if (status) HIP_TRY(st_d.download(status, n_ein));
+  if (status) NDPP_TRY(st_d.download(status, n_ein));
   return NDPP_OK;
 }
 
@@ -1298,19 +1317,19 @@ int ndpp_dev_free(void* p) {
 int ndpp_dev_upload(void* dst_d, const void* src, size_t bytes) {
   if (!bytes) return NDPP_OK;
   if (!dst_d || !src) return fail(NDPP_EINVAL, "NULL pointer");
-  HIP_TRY(hipMemcpy(dst_d, src, bytes, hipMemcpyHostToDevice));
+  NDPP_TRY(hipMemcpy(dst_d, src, bytes, hipMemcpyHostToDevice));
   return NDPP_OK;
 }
 
 int ndpp_dev_download(void* dst, const void* src_d, size_t bytes) {
   if (!bytes) return NDPP_OK;
   if (!dst || !src_d) return fail(NDPP_EINVAL, "NULL pointer");
-  HIP_TRY(hipMemcpy(dst, src_d, bytes, hipMemcpyDeviceToHost));
+  NDPP_TRY(hipMemcpy(dst, src_d, bytes, hipMemcpyDeviceToHost));
   return NDPP_OK;
 }
 
 int ndpp_dev_synchronize(void) {
-  HIP_TRY(hipDeviceSynchronize());
+  NDPP_TRY(hipDeviceSynchronize());
   return NDPP_OK;
 }
 
@@ -1322,7 +1341,7 @@ int ndpp_reserve_workspace(size_t bytes) {
   std::lock_guard<std::mutex> lock(ws->mu);
   if (bytes == 0) {   // what the largest batch may take: min(60 % of free HBM, 128 GB)
     size_t free_b = 0, total_b = 0;
-    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+    NDPP_TRY(hipMemGetInfo(&free_b, &total_b));
     if (ws->base) free_b += ws->bytes;
     bytes = std::min<size_t>((size_t)(free_b * 0.6), (size_t)128 << 30);
   }
@@ -1377,7 +1396,7 @@ int ndpp_set_device(int device) {
   if (int rc = require_device()) return rc;
   const int ndev = ndpp_device_count();
   if (device < 0 || device >= ndev) return fail(NDPP_EINVAL, "device %d outside 0..%d", device, ndev - 1);
-  HIP_TRY(hipSetDevice(device));
+  NDPP_TRY(hipSetDevice(device));
   return NDPP_OK;
 }
 
@@ -1464,23 +1483,23 @@ int ndpp_elastic_leg_multi(const ndpp_params* p, int n_nuc, const double* A, con
   const size_t GL = (size_t)G * p->order, M = (size_t)p->mu_bins;
   DevBuf<double> dA, dkT, dcut, dQ, dein, dw, df, dbins, dout;
   DevBuf<int> dnuc, drow, dst;
-  HIP_TRY(dA.upload(A, n_nuc));
-  HIP_TRY(dkT.upload(kT, n_nuc));
-  HIP_TRY(dcut.upload(freegas_cutoff, n_nuc));
-  HIP_TRY(dQ.upload(Q, n_nuc));
-  HIP_TRY(dein.upload(ein, n_ein));
-  HIP_TRY(dnuc.upload(nuc_of_ein, n_ein));
-  HIP_TRY(drow.upload(row_lo, n_ein));
-  HIP_TRY(dw.upload(w_hi, n_ein));
-  HIP_TRY(df.upload(f_tab, (size_t)n_rows * M));
-  HIP_TRY(dbins.upload(e_bins, G + 1));
-  HIP_TRY(dout.alloc(n_ein * GL));
-  HIP_TRY(dst.alloc(n_ein));
+  NDPP_TRY(dA.upload(A, n_nuc));
+  NDPP_TRY(dkT.upload(kT, n_nuc));
+  NDPP_TRY(dcut.upload(freegas_cutoff, n_nuc));
+  NDPP_TRY(dQ.upload(Q, n_nuc));
+  NDPP_TRY(dein.upload(ein, n_ein));
+  NDPP_TRY(dnuc.upload(nuc_of_ein, n_ein));
+  NDPP_TRY(drow.upload(row_lo, n_ein));
+  NDPP_TRY(dw.upload(w_hi, n_ein));
+  NDPP_TRY(df.upload(f_tab, (size_t)n_rows * M));
+  NDPP_TRY(dbins.upload(e_bins, G + 1));
+  NDPP_TRY(dout.alloc(n_ein * GL));
+  NDPP_TRY(dst.alloc(n_ein));
   rc = ndpp_elastic_leg_multi_d(p, n_nuc, dA.p, dkT.p, dcut.p, dQ.p, n_ein, dein.p, dnuc.p, drow.p, dw.p, n_rows,
                                 df.p, G, dbins.p, dout.p, dst.p, nullptr, stats);
   if (rc) return rc;
-  HIP_TRY(dout.download(out, n_ein * GL));
-  if (status) HIP_TRY(dst.download(status, n_ein));
+  NDPP_TRY(dout.download(out, n_ein * GL));
+  if (status) NDPP_TRY(dst.download(status, n_ein));
   return NDPP_OK;
 }
 

@@ -537,11 +537,8 @@ int integrate_reaction(const Call& c, const SD& sd, int kind, double cutoff, con
     for (int k = 0; k < sd.NE; ++k)
       std::copy(sd.f.begin() + (size_t)sd.row_ptr[k] * c.M, sd.f.begin() + (size_t)(sd.row_ptr[k] + 1) * c.M,
                 ftab.begin() + (size_t)k * c.M);
-    return c.n_tab > 0
-               ? law9_tab_batch_sink(c.p, s.nb, s.ein.data(), s.row_lo.data(), s.w_hi.data(), sd.NE, ftab.data(),
-                                     sd.edist->n_data, sd.edist->data, c.G, c.e_bins, c.n_tab, res, status.data(), sink)
-               : law9_leg_batch_sink(c.p, s.nb, s.ein.data(), s.row_lo.data(), s.w_hi.data(), sd.NE, ftab.data(),
-                                     sd.edist->n_data, sd.edist->data, c.G, c.e_bins, res, status.data(), sink);
+    return law9_batch_sink(c.p, s.nb, s.ein.data(), s.row_lo.data(), s.w_hi.data(), sd.NE, ftab.data(),
+                           sd.edist->n_data, sd.edist->data, c.G, c.e_bins, c.n_tab, res, status.data(), sink);
   }
   return file6_batch_sink(c.p, nuc->awr, kind == 2 ? 1 : 0, s.nb, s.ein.data(), s.row_lo.data(), sd.NE,
                           sd.e_grid.data(), sd.row_ptr.data(), sd.eout.data(), sd.pdf.data(), sd.intt.data(),

@@ -247,15 +247,6 @@ __global__ void apply_tol_kernel(int L, int G, int n, double* data, double tol) 
   }
 }
 
-
-
-#define SAB_TRY(expr)                                                             \
-  do {                                                                            \
-    hipError_t e_ = (expr);                                                       \
-    if (e_ != hipSuccess)                                                         \
-      return fail(NDPP_EDEVICE, "%s failed: %s", #expr, hipGetErrorString(e_));   \
-  } while (0)
-
 }  // namespace
 }  // namespace ndpp
 
@@ -277,9 +268,7 @@ extern "C" int ndpp_sab_batch(const ndpp_params* p, const ndpp_sab_flat* t, int 
     return fail(NDPP_EINVAL, "secondary_mode=%d", mode);
   if (mode == SAB_SECONDARY_SKEWED && NEo <= 4)  // reference: fatal_error, sab.F90:183
     return fail(NDPP_EINVAL, "skewed weighting needs more than 4 outgoing energies");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-    return fail(NDPP_EDEVICE, "no HIP device available (libndpp_hip has no CPU path)");
+  if (int rc = require_device()) return rc;
 
   const int L = p->order;
   const size_t nout = (size_t)n_ein * G * L;
@@ -302,11 +291,11 @@ extern "C" int ndpp_sab_batch(const ndpp_params* p, const ndpp_sab_flat* t, int 
   DevBuf<double> d_ei, d_sig, d_eo, d_mu, d_ce, d_cp, d_cm, d_ee, d_eP, d_emu, d_ein, d_bins, d_w,
       d_distro, d_el, d_inel, d_mat;
   DevBuf<int> d_cptr, d_st;
-  SAB_TRY(d_ei.upload(t->inelastic_e_in, NEi));
-  SAB_TRY(d_sig.upload(t->inelastic_sigma, NEi));
+  NDPP_TRY(d_ei.upload(t->inelastic_e_in, NEi));
+  NDPP_TRY(d_sig.upload(t->inelastic_sigma, NEi));
   if (mode != SAB_SECONDARY_CONT) {
-    SAB_TRY(d_eo.upload(t->inelastic_e_out, (size_t)NEi * NEo));
-    SAB_TRY(d_mu.upload(t->inelastic_mu, (size_t)NEi * NEo * NMU));
+    NDPP_TRY(d_eo.upload(t->inelastic_e_out, (size_t)NEi * NEo));
+    NDPP_TRY(d_mu.upload(t->inelastic_mu, (size_t)NEi * NEo * NMU));
   } else {
     if (!t->cont_ptr) return fail(NDPP_EINVAL, "continuous mode without cont_ptr");
     if (t->cont_ptr[0] != 0) return fail(NDPP_EINVAL, "cont_ptr[0] must be 0");
@@ -314,27 +303,27 @@ extern "C" int ndpp_sab_batch(const ndpp_params* p, const ndpp_sab_flat* t, int 
     for (int k = 0; k < NEi; ++k)
       if (t->cont_ptr[k + 1] - t->cont_ptr[k] < 2)
         return fail(NDPP_EINVAL, "continuous row %d has < 2 outgoing energies", k);
-    SAB_TRY(d_cptr.upload(t->cont_ptr, NEi + 1));
-    SAB_TRY(d_ce.upload(t->cont_e_out, tot));
-    SAB_TRY(d_cp.upload(t->cont_pdf, tot));
-    SAB_TRY(d_cm.upload(t->cont_mu, tot * NMU));
+    NDPP_TRY(d_cptr.upload(t->cont_ptr, NEi + 1));
+    NDPP_TRY(d_ce.upload(t->cont_e_out, tot));
+    NDPP_TRY(d_cp.upload(t->cont_pdf, tot));
+    NDPP_TRY(d_cm.upload(t->cont_mu, tot * NMU));
   }
   if (t->threshold_elastic != 0.0) {
     if (t->n_elastic_e_in < 2) return fail(NDPP_EINVAL, "elastic data needs >= 2 E_in");
-    SAB_TRY(d_ee.upload(t->elastic_e_in, t->n_elastic_e_in));
-    SAB_TRY(d_eP.upload(t->elastic_P, t->n_elastic_e_in));
+    NDPP_TRY(d_ee.upload(t->elastic_e_in, t->n_elastic_e_in));
+    NDPP_TRY(d_eP.upload(t->elastic_P, t->n_elastic_e_in));
     if (t->n_elastic_mu > 0)
-      SAB_TRY(d_emu.upload(t->elastic_mu, (size_t)t->n_elastic_e_in * t->n_elastic_mu));
+      NDPP_TRY(d_emu.upload(t->elastic_mu, (size_t)t->n_elastic_e_in * t->n_elastic_mu));
   }
-  SAB_TRY(d_ein.upload(ein, n_ein));
-  SAB_TRY(d_bins.upload(e_bins, G + 1));
-  SAB_TRY(d_w.upload(wgt.data(), wgt.size()));
-  SAB_TRY(d_distro.alloc((size_t)NEi * G * L));
-  SAB_TRY(d_el.alloc(nout));
-  SAB_TRY(d_inel.alloc(nout));
-  SAB_TRY(d_mat.alloc(nout));
-  SAB_TRY(d_st.alloc(n_ein));
-  SAB_TRY(hipMemset(d_st.p, 0, sizeof(int) * n_ein));
+  NDPP_TRY(d_ein.upload(ein, n_ein));
+  NDPP_TRY(d_bins.upload(e_bins, G + 1));
+  NDPP_TRY(d_w.upload(wgt.data(), wgt.size()));
+  NDPP_TRY(d_distro.alloc((size_t)NEi * G * L));
+  NDPP_TRY(d_el.alloc(nout));
+  NDPP_TRY(d_inel.alloc(nout));
+  NDPP_TRY(d_mat.alloc(nout));
+  NDPP_TRY(d_st.alloc(n_ein));
+  NDPP_TRY(hipMemset(d_st.p, 0, sizeof(int) * n_ein));
   D.t.inelastic_e_in = d_ei.p; D.t.inelastic_sigma = d_sig.p;
   D.t.inelastic_e_out = d_eo.p; D.t.inelastic_mu = d_mu.p;
   D.t.cont_ptr = d_cptr.p; D.t.cont_e_out = d_ce.p; D.t.cont_pdf = d_cp.p; D.t.cont_mu = d_cm.p;
@@ -352,11 +341,11 @@ extern "C" int ndpp_sab_batch(const ndpp_params* p, const ndpp_sab_flat* t, int 
   }
   hipLaunchKernelGGL(sab_combine_kernel, dim3(nblk(n_ein, 128)), dim3(128), 0, 0, D);
   span.end();
-  SAB_TRY(hipGetLastError());
-  SAB_TRY(hipDeviceSynchronize());
-  SAB_TRY(hipMemcpy(scatt_mat, d_mat.p, sizeof(double) * nout, hipMemcpyDeviceToHost));
-  if (el) SAB_TRY(hipMemcpy(el, d_el.p, sizeof(double) * nout, hipMemcpyDeviceToHost));
-  if (inel) SAB_TRY(hipMemcpy(inel, d_inel.p, sizeof(double) * nout, hipMemcpyDeviceToHost));
+  NDPP_TRY(hipGetLastError());
+  NDPP_TRY(hipDeviceSynchronize());
+  NDPP_TRY(hipMemcpy(scatt_mat, d_mat.p, sizeof(double) * nout, hipMemcpyDeviceToHost));
+  if (el) NDPP_TRY(hipMemcpy(el, d_el.p, sizeof(double) * nout, hipMemcpyDeviceToHost));
+  if (inel) NDPP_TRY(hipMemcpy(inel, d_inel.p, sizeof(double) * nout, hipMemcpyDeviceToHost));
   return NDPP_OK;
 }
 
@@ -364,15 +353,13 @@ extern "C" int ndpp_apply_tol_scatt(int L, int G, int n, double* data, double to
   if (L < 1 || G < 1 || n < 0) return fail(NDPP_EINVAL, "L=%d G=%d n=%d", L, G, n);
   if (n == 0) return NDPP_OK;
   if (!data) return fail(NDPP_EINVAL, "NULL data");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-    return fail(NDPP_EDEVICE, "no HIP device available (libndpp_hip has no CPU path)");
+  if (int rc = require_device()) return rc;
   DevBuf<double> d;
   const size_t tot = (size_t)n * G * L;
-  SAB_TRY(d.upload(data, tot));
+  NDPP_TRY(d.upload(data, tot));
   hipLaunchKernelGGL(apply_tol_kernel, dim3(nblk(n, 128)), dim3(128), 0, 0, L, G, n, d.p, tol);
-  SAB_TRY(hipGetLastError());
-  SAB_TRY(hipDeviceSynchronize());
-  SAB_TRY(hipMemcpy(data, d.p, sizeof(double) * tot, hipMemcpyDeviceToHost));
+  NDPP_TRY(hipGetLastError());
+  NDPP_TRY(hipDeviceSynchronize());
+  NDPP_TRY(hipMemcpy(data, d.p, sizeof(double) * tot, hipMemcpyDeviceToHost));
   return NDPP_OK;
 }

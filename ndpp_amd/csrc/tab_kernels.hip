@@ -335,18 +335,6 @@ __global__ __launch_bounds__(64) void law9_tab_kernel(int n_ein, const double* e
   }
 }
 
-// (1-f)*lo + f*hi, :628,:636
-__global__ void law9_tab_blend(int n_ein, const double* w_hi, const double* raw, int GN, double* out, int* status) {
-  const long tot = (long)n_ein * GN;
-  for (long t = blockIdx.x * (long)blockDim.x + threadIdx.x; t < tot; t += (long)gridDim.x * blockDim.x) {
-    const int e = (int)(t / GN), k = (int)(t % GN);
-    const double f = w_hi[e];
-    const double r = (1.0 - f) * raw[((size_t)2 * e) * GN + k];
-    out[t] = r + f * raw[((size_t)2 * e + 1) * GN + k];
-    if (k == 0) status[e] = 0;
-  }
-}
-
 // ---- free gas --------------------------------------------------------------------------------
 // calc_fgk (freegas.F90:415-473) at l = 0 for the two bracketing rows at once: only f(mu) depends
 // on the row
@@ -572,29 +560,13 @@ __global__ void fg_tab_finish(FgTab P, const double* w_hi, double* out) {
   }
 }
 
-#define TAB_TRY(expr)                                                             \
-  do {                                                                            \
-    hipError_t e_ = (expr);                                                       \
-    if (e_ != hipSuccess)                                                         \
-      return fail(NDPP_EDEVICE, "%s failed: %s", #expr, hipGetErrorString(e_));   \
-  } while (0)
-
-int check_tab(const ndpp_params* p, int n_tab, int G) {
-  if (!p) return fail(NDPP_EINVAL, "params is NULL");
-  if (n_tab < 1 || n_tab > NDPP_MAX_TAB_BINS)
-    return fail(NDPP_EINVAL, "n_tab=%d outside 1..%d", n_tab, NDPP_MAX_TAB_BINS);
-  if (p->mu_bins < 2) return fail(NDPP_EINVAL, "mu_bins=%d < 2", p->mu_bins);
-  if (G < 1) return fail(NDPP_EINVAL, "need at least one group");
-  return NDPP_OK;
-}
-int check_device() {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-    return fail(NDPP_EDEVICE, "no HIP device available (libndpp_hip has no CPU path)");
-  return NDPP_OK;
-}
-
 }  // namespace
+
+void launch_law9_tab(int n_ein, const double* ein, const int* row_lo, int mu_bins, const double* f_tab,
+                     const double* edata, int G, int N, const double* e_bins, double* raw) {
+  hipLaunchKernelGGL(law9_tab_kernel, dim3(nblk((long)n_ein * 2 * G, 64)), dim3(64), 0, 0, n_ein, ein, row_lo,
+                     make_mu_grid(mu_bins), f_tab, edata, G, N, e_bins, raw);
+}
 
 void launch_f6_tab(const F6Batch& B) {
   if (B.frame_cm) {
@@ -612,16 +584,12 @@ int elastic_tab_batch_sink(const ndpp_params* p, double A, double kT, double fre
                            const double* ein, const int* row_lo, const double* w_hi, int n_rows,
                            const double* f_tab, int G, const double* e_bins, int n_tab, double* out, int* status,
                            DeviceSink* sink) {
-  int rc = check_tab(p, n_tab, G);
+  int rc = check_params(p, G, kCheckTab, n_tab);
   if (rc) return rc;
   if (n_ein < 0 || n_rows < 2) return fail(NDPP_EINVAL, "n_ein=%d n_rows=%d", n_ein, n_rows);
   if (n_ein == 0) return NDPP_OK;
   if (!ein || !row_lo || !w_hi || !f_tab || !e_bins || (!out && !sink)) return fail(NDPP_EINVAL, "NULL argument");
-  for (int i = 0; i < n_ein; ++i)
-    if (row_lo[i] < 0 || row_lo[i] + 1 >= n_rows)
-      return fail(NDPP_EINVAL, "row_lo[%d]=%d outside [0, n_rows-2]", i, row_lo[i]);
-  rc = check_device();
-  if (rc) return rc;
+  if ((rc = check_row_lo(n_ein, row_lo, n_rows)) || (rc = require_device())) return rc;
   const int N = n_tab, M = p->mu_bins;
   const size_t GN = (size_t)G * N;
   // classify_kernel's rule: an E_in that is not a positive finite number is not integrated (zero
@@ -631,97 +599,32 @@ int elastic_tab_batch_sink(const ndpp_params* p, double A, double kT, double fre
     if (!(ein[i] > 0.0) || !(ein[i] <= DBL_MAX)) st0[i] = NDPP_ST_RANGE;
     else (ein[i] < freegas_cutoff ? fg : f4).push_back(i);
   }
-  DevBuf<double> d_ein, d_w, d_f, d_bins, d_out, d_ws;
-  DevBuf<int> d_row, d_st, d_fg, d_f4;
-  TAB_TRY(d_ein.upload(ein, n_ein));
-  TAB_TRY(d_w.upload(w_hi, n_ein));
-  TAB_TRY(d_row.upload(row_lo, n_ein));
-  TAB_TRY(d_f.upload(f_tab, (size_t)n_rows * M));
-  TAB_TRY(d_bins.upload(e_bins, G + 1));
-  TAB_TRY(d_out.alloc((size_t)n_ein * GN));
-  TAB_TRY(hipMemsetAsync(d_out.p, 0, sizeof(double) * n_ein * GN, 0));
-  TAB_TRY(d_st.upload(st0.data(), n_ein));
+  BatchInputs in;
+  if ((rc = in.upload(n_ein, ein, w_hi, row_lo, (size_t)n_rows * M, f_tab, G, e_bins))) return rc;
+  DevBuf<double> d_out, d_ws;
+  DevBuf<int> d_st, d_fg, d_f4;
+  NDPP_TRY(d_out.alloc((size_t)n_ein * GN));
+  NDPP_TRY(hipMemsetAsync(d_out.p, 0, sizeof(double) * n_ein * GN, 0));
+  NDPP_TRY(d_st.upload(st0.data(), n_ein));
   const MuGrid grid = make_mu_grid(M);
   GpuSpan span(nullptr, kProfFile4);
   if (!f4.empty()) {
-    TAB_TRY(d_f4.upload(f4.data(), f4.size()));
+    NDPP_TRY(d_f4.upload(f4.data(), f4.size()));
     const long tot = (long)f4.size() * G;
-    hipLaunchKernelGGL(f4_tab_kernel, dim3(nblk(tot, 64)), dim3(64), 0, 0, (int)f4.size(), d_f4.p, grid, d_ein.p,
-                       d_row.p, d_w.p, d_f.p, A, Q, G, N, d_bins.p, d_out.p);
+    hipLaunchKernelGGL(f4_tab_kernel, dim3(nblk(tot, 64)), dim3(64), 0, 0, (int)f4.size(), d_f4.p, grid, in.ein.p,
+                       in.row_lo.p, in.w_hi.p, in.f_tab.p, A, Q, G, N, in.e_bins.p, d_out.p);
   }
   if (!fg.empty()) {
-    TAB_TRY(d_fg.upload(fg.data(), fg.size()));
-    TAB_TRY(d_ws.alloc(fg.size() * GN * 6));
+    NDPP_TRY(d_fg.upload(fg.data(), fg.size()));
+    NDPP_TRY(d_ws.alloc(fg.size() * GN * 6));
     FgTab P;
-    P.n = (int)fg.size(); P.G = G; P.N = N; P.list = d_fg.p; P.ein = d_ein.p; P.row_lo = d_row.p;
-    P.f_tab = d_f.p; P.e_bins = d_bins.p; P.A = A; P.kT = kT; P.sab_threshold = p->sab_threshold;
+    P.n = (int)fg.size(); P.G = G; P.N = N; P.list = d_fg.p; P.ein = in.ein.p; P.row_lo = in.row_lo.p;
+    P.f_tab = in.f_tab.p; P.e_bins = in.e_bins.p; P.A = A; P.kT = kT; P.sab_threshold = p->sab_threshold;
     P.brent_thresh = p->brent_mu_thresh; P.grid = grid; P.ws = d_ws.p; P.status = d_st.p;
     hipLaunchKernelGGL(fg_tab_kernel, dim3(nblk((long)P.n * G, 64)), dim3(64), 0, 0, P);
-    hipLaunchKernelGGL(fg_tab_finish, dim3(nblk(P.n, 64)), dim3(64), 0, 0, P, d_w.p, d_out.p);
+    hipLaunchKernelGGL(fg_tab_finish, dim3(nblk(P.n, 64)), dim3(64), 0, 0, P, in.w_hi.p, d_out.p);
   }
-  hipLaunchKernelGGL(nonfinite_status_kernel, dim3(nblk(n_ein, 64)), dim3(64), 0, 0, n_ein, (int)GN, d_out.p,
-                     d_st.p, 0);
-  span.end();
-  TAB_TRY(hipGetLastError());
-  if (sink) {
-    rc = sink->consume(d_out.p, n_ein, GN);
-    if (rc) return rc;
-  }
-  TAB_TRY(hipDeviceSynchronize());
-  if (!sink) TAB_TRY(hipMemcpy(out, d_out.p, sizeof(double) * n_ein * GN, hipMemcpyDeviceToHost));
-  if (status) TAB_TRY(hipMemcpy(status, d_st.p, sizeof(int) * n_ein, hipMemcpyDeviceToHost));
-  return NDPP_OK;
-}
-
-int law9_tab_batch_sink(const ndpp_params* p, int n_ein, const double* ein, const int* row_lo, const double* w_hi,
-                        int n_rows, const double* f_tab, int n_edata, const double* edata, int G,
-                        const double* e_bins, int n_tab, double* out, int* status, DeviceSink* sink) {
-  int rc = check_tab(p, n_tab, G);
-  if (rc) return rc;
-  if (n_ein < 0 || n_rows < 2 || n_edata < 5) return fail(NDPP_EINVAL, "bad sizes");
-  if (n_ein == 0) return NDPP_OK;
-  if (!ein || !row_lo || !w_hi || !f_tab || !edata || !e_bins || (!out && !sink))
-    return fail(NDPP_EINVAL, "NULL argument");
-  for (int i = 0; i < n_ein; ++i)
-    if (row_lo[i] < 0 || row_lo[i] + 1 >= n_rows)
-      return fail(NDPP_EINVAL, "row_lo[%d]=%d outside [0, n_rows-2]", i, row_lo[i]);
-  {
-    const int NR = (int)edata[0];
-    if (NR < 0 || 2 + 2 * NR > n_edata) return fail(NDPP_EINVAL, "edata: bad NR");
-    const int NE = (int)edata[1 + 2 * NR];
-    if (NE < 1 || 2 + 2 * NR + 2 * NE + 1 > n_edata) return fail(NDPP_EINVAL, "edata: bad NE");
-  }
-  rc = check_device();
-  if (rc) return rc;
-  const int N = n_tab, M = p->mu_bins, GN = G * N;
-  DevBuf<double> d_ein, d_w, d_f, d_ed, d_bins, d_raw, d_out;
-  DevBuf<int> d_row, d_st;
-  TAB_TRY(d_ein.upload(ein, n_ein));
-  TAB_TRY(d_w.upload(w_hi, n_ein));
-  TAB_TRY(d_row.upload(row_lo, n_ein));
-  TAB_TRY(d_f.upload(f_tab, (size_t)n_rows * M));
-  TAB_TRY(d_ed.upload(edata, n_edata));
-  TAB_TRY(d_bins.upload(e_bins, G + 1));
-  TAB_TRY(d_raw.alloc((size_t)n_ein * 2 * GN));
-  TAB_TRY(d_out.alloc((size_t)n_ein * GN));
-  TAB_TRY(d_st.alloc(n_ein));
-  const MuGrid grid = make_mu_grid(M);
-  GpuSpan span(nullptr, kProfLaw9);
-  hipLaunchKernelGGL(law9_tab_kernel, dim3(nblk((long)n_ein * 2 * G, 64)), dim3(64), 0, 0, n_ein, d_ein.p, d_row.p,
-                     grid, d_f.p, d_ed.p, G, N, d_bins.p, d_raw.p);
-  hipLaunchKernelGGL(law9_tab_blend, dim3(nblk((long)n_ein * GN, 256)), dim3(256), 0, 0, n_ein, d_w.p, d_raw.p, GN,
-                     d_out.p, d_st.p);
-  hipLaunchKernelGGL(nonfinite_status_kernel, dim3(nblk(n_ein, 64)), dim3(64), 0, 0, n_ein, GN, d_out.p, d_st.p, 0);
-  span.end();
-  TAB_TRY(hipGetLastError());
-  if (sink) {
-    rc = sink->consume(d_out.p, n_ein, (size_t)GN);
-    if (rc) return rc;
-  }
-  TAB_TRY(hipDeviceSynchronize());
-  if (!sink) TAB_TRY(hipMemcpy(out, d_out.p, sizeof(double) * (size_t)n_ein * GN, hipMemcpyDeviceToHost));
-  if (status) TAB_TRY(hipMemcpy(status, d_st.p, sizeof(int) * n_ein, hipMemcpyDeviceToHost));
-  return NDPP_OK;
+  return finish_batch(d_out.p, d_st.p, n_ein, GN, 0, out, status, sink, span);
 }
 
 }  // namespace ndpp
@@ -751,6 +654,7 @@ extern "C" int ndpp_file6_tab_batch(const ndpp_params* p, int n_tab, double awr,
 extern "C" int ndpp_law9_tab_batch(const ndpp_params* p, int n_tab, int n_ein, const double* ein, const int* row_lo,
                                    const double* w_hi, int n_rows, const double* f_tab, int n_edata,
                                    const double* edata, int G, const double* e_bins, double* out, int* status) {
-  return law9_tab_batch_sink(p, n_ein, ein, row_lo, w_hi, n_rows, f_tab, n_edata, edata, G, e_bins, n_tab, out,
-                             status, nullptr);
+  if (n_tab < 1) return check_params(p, G, kCheckTab, n_tab);     // (n_tab = 0 would ask the sink for moments)
+  return law9_batch_sink(p, n_ein, ein, row_lo, w_hi, n_rows, f_tab, n_edata, edata, G, e_bins, n_tab, out, status,
+                         nullptr);
 }

@@ -145,13 +145,6 @@ thin_fold_kernel(int n, int W, int C, const int* __restrict__ first, const doubl
   }
 }
 
-#define THIN_TRY(expr)                                                            \
-  do {                                                                            \
-    hipError_t e_ = (expr);                                                       \
-    if (e_ != hipSuccess)                                                         \
-      return fail(NDPP_EDEVICE, "%s failed: %s", #expr, hipGetErrorString(e_));   \
-  } while (0)
-
 // the argument checks both entry points share; NDPP_OK or what fail() returned
 int check_args(const char* who, int L, int G, int n, const double* x, const double* y, int n_keep,
                const double* tokeep, int window) {
@@ -176,9 +169,7 @@ int check_args(const char* who, int L, int G, int n, const double* x, const doub
 int segments(const char* who, int L, int G, int n, const double* x, const double* y, const double* y2,
              int n_keep, const double* tokeep, int W, double* seg_err) {
   const int GL = G * L;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-    return fail(NDPP_EDEVICE, "%s: no HIP device available (libndpp_hip has no CPU path)", who);
+  if (int rc = require_device(who)) return rc;
 
   std::vector<double> lx((size_t)n), s((size_t)n), s2(y2 ? (size_t)n : 0);
   std::vector<unsigned char> flags((size_t)n, 0);
@@ -217,31 +208,31 @@ int segments(const char* who, int L, int G, int n, const double* x, const double
   DevBuf<double> d_lx, d_s, d_s2, d_y, d_y2, d_part, d_seg;
   DevBuf<unsigned char> d_flags;
   DevBuf<int> d_items, d_first;
-  THIN_TRY(d_lx.upload(lx.data(), lx.size()));
-  THIN_TRY(d_s.upload(s.data(), s.size()));
-  if (y2) THIN_TRY(d_s2.upload(s2.data(), s2.size()));
-  THIN_TRY(d_flags.upload(flags.data(), flags.size()));
-  THIN_TRY(d_items.upload(items.data(), items.size()));
-  THIN_TRY(d_first.upload(first.data(), first.size()));
-  THIN_TRY(d_y.upload(y, (size_t)n * GL));
-  if (y2) THIN_TRY(d_y2.upload(y2, (size_t)n * GL));
-  THIN_TRY(d_part.alloc((size_t)std::max(n_anchor, 1) * C));
-  THIN_TRY(d_seg.alloc((size_t)n * (W - 1)));
+  NDPP_TRY(d_lx.upload(lx.data(), lx.size()));
+  NDPP_TRY(d_s.upload(s.data(), s.size()));
+  if (y2) NDPP_TRY(d_s2.upload(s2.data(), s2.size()));
+  NDPP_TRY(d_flags.upload(flags.data(), flags.size()));
+  NDPP_TRY(d_items.upload(items.data(), items.size()));
+  NDPP_TRY(d_first.upload(first.data(), first.size()));
+  NDPP_TRY(d_y.upload(y, (size_t)n * GL));
+  if (y2) NDPP_TRY(d_y2.upload(y2, (size_t)n * GL));
+  NDPP_TRY(d_part.alloc((size_t)std::max(n_anchor, 1) * C));
+  NDPP_TRY(d_seg.alloc((size_t)n * (W - 1)));
   {
     GpuSpan span(nullptr, -1);
     if (n_anchor > 0) {
       const dim3 grid((unsigned)((n_anchor + A - 1) / A), (unsigned)((A * C + kThreads - 1) / kThreads));
       hipLaunchKernelGGL(thin_partial_kernel, grid, dim3(kThreads), 0, 0, n, GL, W, A, C, d_items.p, d_lx.p, d_s.p,
                          y2 ? d_s2.p : nullptr, d_flags.p, d_y.p, y2 ? d_y2.p : nullptr, d_part.p);
-      THIN_TRY(hipGetLastError());
+      NDPP_TRY(hipGetLastError());
     }
     hipLaunchKernelGGL(thin_fold_kernel, dim3(nblk((long)n * (W - 1), kThreads)), dim3(kThreads), 0, 0, n, W, C,
                        d_first.p, d_part.p, d_seg.p);
     span.end();
-    THIN_TRY(hipGetLastError());
-    THIN_TRY(hipDeviceSynchronize());
+    NDPP_TRY(hipGetLastError());
+    NDPP_TRY(hipDeviceSynchronize());
   }
-  THIN_TRY(d_seg.download(seg_err, (size_t)n * (W - 1)));
+  NDPP_TRY(d_seg.download(seg_err, (size_t)n * (W - 1)));
   return NDPP_OK;
 }
 

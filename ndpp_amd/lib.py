@@ -635,8 +635,16 @@ def _dp(a: np.ndarray):
     return a.ctypes.data_as(c_double_p)
 
 
+def _ip(a: np.ndarray):
+    return a.ctypes.data_as(c_int_p)
+
+
 def _f64(a) -> np.ndarray:
     return np.ascontiguousarray(a, dtype=np.float64)
+
+
+def _i32(a) -> np.ndarray:
+    return np.ascontiguousarray(a, dtype=np.int32)
 
 
 def mu_grid(mu_bins: int) -> np.ndarray:
@@ -682,26 +690,31 @@ def integrate_file4_cm_leg(fw, Ein, awr, Q, E_bins, w, order, params: Params | N
     return out.T.copy()
 
 
+def _bracket_args(ein, row_lo, w_hi, f_tab, e_bins):
+    """The arrays of a bracketed-row batch call as the C ABI takes them."""
+    ein, w_hi, f_tab, e_bins = map(_f64, (ein, w_hi, f_tab, e_bins))
+    return ein, _i32(row_lo), w_hi, f_tab, e_bins
+
+
+def _batch_out(params: Params, mu_bins, n, G, n_tab=None):
+    """params with the table's mu_bins, out[n][G][order, or n_tab bins] and status[n] of a batch call."""
+    p = Params.from_buffer_copy(params)
+    p.mu_bins = mu_bins
+    out = np.zeros((n, G, p.order if n_tab is None else max(int(n_tab), 0)))
+    return p, out, np.zeros(n, dtype=np.int32)
+
+
 def elastic_leg_batch(params: Params, A, kT, freegas_cutoff, Q, ein, row_lo, w_hi,
                       f_tab, e_bins, want_stats: bool = False):
     """Host-array front end of ndpp_elastic_leg_batch. Returns out[n_ein][G][L],
     status[n_ein] (and Stats)."""
-    ein = _f64(ein)
-    row_lo = np.ascontiguousarray(row_lo, dtype=np.int32)
-    w_hi = _f64(w_hi)
-    f_tab = _f64(f_tab)
-    e_bins = _f64(e_bins)
-    n = ein.shape[0]
-    G = e_bins.shape[0] - 1
-    p = Params.from_buffer_copy(params)
-    p.mu_bins = f_tab.shape[1]
-    out = np.zeros((n, G, p.order))
-    status = np.zeros(n, dtype=np.int32)
+    ein, row_lo, w_hi, f_tab, e_bins = _bracket_args(ein, row_lo, w_hi, f_tab, e_bins)
+    n, G = ein.shape[0], e_bins.shape[0] - 1
+    p, out, status = _batch_out(params, f_tab.shape[1], n, G)
     st = Stats()
     _check(load().ndpp_elastic_leg_batch(
-        C.byref(p), A, kT, freegas_cutoff, Q, n, _dp(ein), row_lo.ctypes.data_as(c_int_p),
-        _dp(w_hi), f_tab.shape[0], _dp(f_tab), G, _dp(e_bins), _dp(out),
-        status.ctypes.data_as(c_int_p), C.byref(st)))
+        C.byref(p), A, kT, freegas_cutoff, Q, n, _dp(ein), _ip(row_lo), _dp(w_hi), f_tab.shape[0], _dp(f_tab), G,
+        _dp(e_bins), _dp(out), _ip(status), C.byref(st)))
     return (out, status, st) if want_stats else (out, status)
 
 
@@ -726,8 +739,16 @@ def elastic_leg_batch_device(params: Params, A, kT, freegas_cutoff, Q, ein_t, ro
     return st
 
 
-def _ip(a: np.ndarray):
-    return a.ctypes.data_as(c_int_p)
+def _file6_batch(params: Params, n_tab, awr, frame_cm, ein, row_lo, e_grid, row_ptr, eout, pdf, intt, f, e_bins):
+    ein, e_grid, eout, pdf, f, e_bins = map(_f64, (ein, e_grid, eout, pdf, f, e_bins))
+    row_lo, row_ptr, intt = map(_i32, (row_lo, row_ptr, intt))
+    G = e_bins.shape[0] - 1
+    p, out, status = _batch_out(params, f.shape[1], len(ein), G, n_tab)
+    lib = load()
+    fn, head = (lib.ndpp_file6_leg_batch, ()) if n_tab is None else (lib.ndpp_file6_tab_batch, (int(n_tab),))
+    _check(fn(C.byref(p), *head, awr, int(bool(frame_cm)), len(ein), _dp(ein), _ip(row_lo), len(e_grid), _dp(e_grid),
+              _ip(row_ptr), _dp(eout), _dp(pdf), _ip(intt), _dp(f), G, _dp(e_bins), _dp(out), _ip(status)))
+    return out, status
 
 
 def file6_leg_batch(params: Params, awr, frame_cm, ein, row_lo, e_grid, row_ptr, eout, pdf,
@@ -735,37 +756,25 @@ def file6_leg_batch(params: Params, awr, frame_cm, ein, row_lo, e_grid, row_ptr,
     """ndpp_file6_leg_batch: unit-base interpolation + integrate_file6_{cm,lab}_leg
     (scattdata_header.F90:593-656) for a CSR-flattened ScattData.  f is [sum NP][M].
     Returns out[n_ein][G][L], status[n_ein]."""
-    ein = _f64(ein)
-    row_lo = np.ascontiguousarray(row_lo, dtype=np.int32)
-    e_grid, eout, pdf, f, e_bins = map(_f64, (e_grid, eout, pdf, f, e_bins))
-    row_ptr = np.ascontiguousarray(row_ptr, dtype=np.int32)
-    intt = np.ascontiguousarray(intt, dtype=np.int32)
-    p = Params.from_buffer_copy(params)
-    p.mu_bins = f.shape[1]
+    return _file6_batch(params, None, awr, frame_cm, ein, row_lo, e_grid, row_ptr, eout, pdf, intt, f, e_bins)
+
+
+def _law9_batch(params: Params, n_tab, ein, row_lo, w_hi, f_tab, edata, e_bins):
+    ein, row_lo, w_hi, f_tab, e_bins = _bracket_args(ein, row_lo, w_hi, f_tab, e_bins)
+    edata = _f64(edata)
     G = e_bins.shape[0] - 1
-    out = np.zeros((len(ein), G, p.order))
-    status = np.zeros(len(ein), dtype=np.int32)
-    _check(load().ndpp_file6_leg_batch(C.byref(p), awr, int(bool(frame_cm)), len(ein), _dp(ein),
-                                       _ip(row_lo), len(e_grid), _dp(e_grid), _ip(row_ptr),
-                                       _dp(eout), _dp(pdf), _ip(intt), _dp(f), G, _dp(e_bins),
-                                       _dp(out), _ip(status)))
+    p, out, status = _batch_out(params, f_tab.shape[1], len(ein), G, n_tab)
+    lib = load()
+    fn, head = (lib.ndpp_law9_leg_batch, ()) if n_tab is None else (lib.ndpp_law9_tab_batch, (int(n_tab),))
+    _check(fn(C.byref(p), *head, len(ein), _dp(ein), _ip(row_lo), _dp(w_hi), f_tab.shape[0], _dp(f_tab), len(edata),
+              _dp(edata), G, _dp(e_bins), _dp(out), _ip(status)))
     return out, status
 
 
 def law9_leg_batch(params: Params, ein, row_lo, w_hi, f_tab, edata, e_bins):
     """ndpp_law9_leg_batch: law9_scatter_lab_leg on both bracketing rows + blend
     (scattdata_header.F90:605-638)."""
-    ein, w_hi, f_tab, edata, e_bins = map(_f64, (ein, w_hi, f_tab, edata, e_bins))
-    row_lo = np.ascontiguousarray(row_lo, dtype=np.int32)
-    p = Params.from_buffer_copy(params)
-    p.mu_bins = f_tab.shape[1]
-    G = e_bins.shape[0] - 1
-    out = np.zeros((len(ein), G, p.order))
-    status = np.zeros(len(ein), dtype=np.int32)
-    _check(load().ndpp_law9_leg_batch(C.byref(p), len(ein), _dp(ein), _ip(row_lo), _dp(w_hi),
-                                      f_tab.shape[0], _dp(f_tab), len(edata), _dp(edata), G,
-                                      _dp(e_bins), _dp(out), _ip(status)))
-    return out, status
+    return _law9_batch(params, None, ein, row_lo, w_hi, f_tab, edata, e_bins)
 
 
 SCATT_LEGENDRE, SCATT_TABULAR, MAX_TAB_BINS = 0, 1, 128
@@ -774,13 +783,9 @@ SCATT_LEGENDRE, SCATT_TABULAR, MAX_TAB_BINS = 0, 1, 128
 def elastic_tab_batch(params: Params, n_tab, A, kT, freegas_cutoff, Q, ein, row_lo, w_hi, f_tab, e_bins):
     """ndpp_elastic_tab_batch: elastic_leg_batch's P0 split into n_tab lab-cosine bins.
     Returns out[n_ein][G][n_tab], status[n_ein]."""
-    ein, w_hi, f_tab, e_bins = map(_f64, (ein, w_hi, f_tab, e_bins))
-    row_lo = np.ascontiguousarray(row_lo, dtype=np.int32)
+    ein, row_lo, w_hi, f_tab, e_bins = _bracket_args(ein, row_lo, w_hi, f_tab, e_bins)
     n, G = ein.shape[0], e_bins.shape[0] - 1
-    p = Params.from_buffer_copy(params)
-    p.mu_bins = f_tab.shape[1]
-    out = np.zeros((n, G, max(int(n_tab), 0)))
-    status = np.zeros(n, dtype=np.int32)
+    p, out, status = _batch_out(params, f_tab.shape[1], n, G, n_tab)
     _check(load().ndpp_elastic_tab_batch(
         C.byref(p), int(n_tab), A, kT, freegas_cutoff, Q, n, _dp(ein), _ip(row_lo), _dp(w_hi),
         f_tab.shape[0], _dp(f_tab), G, _dp(e_bins), _dp(out), _ip(status), None))
@@ -790,34 +795,12 @@ def elastic_tab_batch(params: Params, n_tab, A, kT, freegas_cutoff, Q, ein, row_
 def file6_tab_batch(params: Params, n_tab, awr, frame_cm, ein, row_lo, e_grid, row_ptr, eout, pdf,
                     intt, f, e_bins):
     """ndpp_file6_tab_batch: file6_leg_batch's P0 in n_tab lab-cosine bins."""
-    ein, e_grid, eout, pdf, f, e_bins = map(_f64, (ein, e_grid, eout, pdf, f, e_bins))
-    row_lo = np.ascontiguousarray(row_lo, dtype=np.int32)
-    row_ptr = np.ascontiguousarray(row_ptr, dtype=np.int32)
-    intt = np.ascontiguousarray(intt, dtype=np.int32)
-    p = Params.from_buffer_copy(params)
-    p.mu_bins = f.shape[1]
-    G = e_bins.shape[0] - 1
-    out = np.zeros((len(ein), G, max(int(n_tab), 0)))
-    status = np.zeros(len(ein), dtype=np.int32)
-    _check(load().ndpp_file6_tab_batch(C.byref(p), int(n_tab), awr, int(bool(frame_cm)), len(ein), _dp(ein),
-                                       _ip(row_lo), len(e_grid), _dp(e_grid), _ip(row_ptr), _dp(eout),
-                                       _dp(pdf), _ip(intt), _dp(f), G, _dp(e_bins), _dp(out), _ip(status)))
-    return out, status
+    return _file6_batch(params, n_tab, awr, frame_cm, ein, row_lo, e_grid, row_ptr, eout, pdf, intt, f, e_bins)
 
 
 def law9_tab_batch(params: Params, n_tab, ein, row_lo, w_hi, f_tab, edata, e_bins):
     """ndpp_law9_tab_batch: law9_leg_batch's P0 in n_tab lab-cosine bins."""
-    ein, w_hi, f_tab, edata, e_bins = map(_f64, (ein, w_hi, f_tab, edata, e_bins))
-    row_lo = np.ascontiguousarray(row_lo, dtype=np.int32)
-    p = Params.from_buffer_copy(params)
-    p.mu_bins = f_tab.shape[1]
-    G = e_bins.shape[0] - 1
-    out = np.zeros((len(ein), G, max(int(n_tab), 0)))
-    status = np.zeros(len(ein), dtype=np.int32)
-    _check(load().ndpp_law9_tab_batch(C.byref(p), int(n_tab), len(ein), _dp(ein), _ip(row_lo), _dp(w_hi),
-                                      f_tab.shape[0], _dp(f_tab), len(edata), _dp(edata), G, _dp(e_bins),
-                                      _dp(out), _ip(status)))
-    return out, status
+    return _law9_batch(params, n_tab, ein, row_lo, w_hi, f_tab, edata, e_bins)
 
 
 def sab_batch(params: Params, table, ein, e_bins, want_parts: bool = False):
