@@ -662,6 +662,64 @@ int ndpp_scatt_positivity(int n_ein, int G, int L, const double *mat, int n_mome
 int ndpp_expand_moments(int n_ein, int L, const double *moments, int n_moments,
                         int n_mu, const double *mu, double *out /* [n_ein][n_mu] */);
 
+/* ---- certified positivity.  Replaces nothing: test_scatt_positivity and
+ * ndpp_scatt_positivity sample f on a grid, and a dip between two grid points passes.  Here every
+ * examined row gets an enclosure  lo <= min over [-1, 1] of f <= hi  of
+ *   f(mu) = sum_{l < n_moments} c_l P_l(mu),   c_l = (l + 1/2) a_l,
+ * with hi = f(mu_at) an attained value.  With
+ *   S  = sum |c_l|                                     (|f| <= S on [-1, 1])
+ *   M2 = sum_{l >= 2} |c_l| (l-1) l (l+1) (l+2) / 8    (|f''| <= M2: |P_l''| is largest at the ends)
+ *   E  = 256 * DBL_EPSILON * S                          (the evaluation allowance)
+ * the enclosure rests on  f >= min(f(a), f(a+h)) - M2 h^2 / 8  on [a, a+h]  (f minus its chord is
+ * f''(xi) (mu-a)(mu-a-h) / 2).
+ * Rows: exactly those ndpp_scatt_positivity examines -- per E_in the groups gmin..gmax, the first and
+ * last with P0 > 0, interior rows with P0 <= 0 included.  An E_in without P0 > 0 is one row, held at
+ * group 0 of the arrays: lo = hi = mu_at = 0, class positive, named as group -1 in the summary.  An
+ * entry outside the band gets cls = -1, lo = hi = mu_at = 0.
+ * Search: f at the 65 nodes of 64 equal panels gives the first hi.  An interval is DISCARDED when
+ *   (min(f(a), f(a+h)) - hi) + rel_tol S >= M2 h^2 / 8
+ * (its bound is within rel_tol S of hi; arranged so that a tiny M2 h^2 / 8 is not absorbed by the
+ * subtraction); otherwise its midpoint is evaluated, hi and mu_at follow a smaller value, and both
+ * halves are examined, at most 45 levels below the panels, where an interval is discarded with
+ * whatever bound it has.  lo = min(smallest discarded bound, hi) - E: a lower bound of the exact
+ * polynomial of the stored doubles.  A row is SETTLED when every interval was discarded by the rule;
+ * then hi - lo <= rel_tol S + E (to the rounding of that expression).  A row makes at most
+ * NDPP_MIN_MAX_EVALS evaluations of f, the nodes (read twice) and re-evaluated interval ends counted;
+ * a row that runs into the cap or into the depth limit returns the valid, wider enclosure it has,
+ * with NDPP_MIN_UNSETTLED set.  No loop on the device depends on convergence alone.
+ * cls: -1 not examined; else the class in the low two bits -- NDPP_MIN_POSITIVE lo >= 0;
+ * NDPP_MIN_NEGATIVE hi < 0 (mu_at is a witness); NDPP_MIN_UNDECIDED lo < 0 <= hi (the minimum is
+ * within the tolerance of zero); NDPP_MIN_NONFINITE a NaN or an infinity among the row's n_moments
+ * moments (or an S or M2 that overflows): lo = hi = NaN, mu_at = 0, never passes -- plus the bit
+ * NDPP_MIN_UNSETTLED.  rel_tol = 0 is legal: rows with M2 = 0 (constant or linear f) settle at once,
+ * the rest come back unsettled.
+ * Arithmetic: P_0 = 1, P_1 = mu, P_{l+1} = (((2l+1) mu) P_l - l P_{l-1}) / (l+1); f = c_0, then
+ * f = f + c_l P_l in ascending l; only + - * / and comparisons, without contraction, in every build:
+ * two calls on the same input return the same bits.  The summary is folded on the host from the
+ * dense arrays in (iE, g) order.
+ * NDPP_EINVAL, decided before the device is touched: L outside 1..NDPP_MAX_ORDER, n_moments outside
+ * 1..L, G < 1, n_ein < 0, rel_tol negative, NaN or infinite, a NULL pointer, sizes whose bytes
+ * overflow.  n_ein = 0 is an empty, successful call.  Without a device NDPP_EDEVICE.              */
+#define NDPP_MIN_MAX_EVALS 16384
+#define NDPP_MIN_POSITIVE  0
+#define NDPP_MIN_UNDECIDED 1
+#define NDPP_MIN_NEGATIVE  2
+#define NDPP_MIN_NONFINITE 3
+#define NDPP_MIN_UNSETTLED 4
+typedef struct ndpp_minimum {
+  long   rows, negative, undecided, nonfinite, unsettled;
+  double min_hi, min_mu;      /* smallest hi over examined finite rows, and its cosine; +inf / 0 if none */
+  int    min_ein, min_group;  /* first row in (iE, g) order attaining it; all-zero E_in: group -1; none: -1, -1 */
+} ndpp_minimum;
+int ndpp_scatt_minimum(int n_ein, int G, int L, const double *mat /* [n_ein][G][L] */, int n_moments,
+                       double rel_tol, double *lo, double *hi, double *mu_at, int *cls /* each [n_ein][G] */,
+                       ndpp_minimum *summary);
+/* the same call, which also returns the evaluations of f each row made (0 where none was needed):
+ * for measurements (tools/bench_minimum.py) and for the test of the cap.  NULL evals: NDPP_EINVAL. */
+int ndpp_scatt_minimum_evals(int n_ein, int G, int L, const double *mat, int n_moments, double rel_tol,
+                             double *lo, double *hi, double *mu_at, int *cls, int *evals /* [n_ein][G] */,
+                             ndpp_minimum *summary);
+
 /* ---- interpolation error of an incoming-energy grid.  Replaces nothing: the reference never
  * measures it (thin_grid compares stored rows with each other, never with a fresh one).
  * x[n] with rows y[n][G][L]; x_mid[n-1] with rows y_mid[n-1][G][L] integrated there.  For

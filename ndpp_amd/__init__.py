@@ -13,6 +13,8 @@ from .lib import (_check, Params, Stats, NdppError, load, library_path, mu_grid,
                   set_device, freegas_rough_rows, mapped_runtimes, profile_reset, profile_get,
                   ST_NONFINITE, ST_RANGE, ST_ORDER_NOISE,
                   Positivity, scatt_positivity, expand_moments,
+                  Minimum, scatt_minimum, MIN_POSITIVE, MIN_UNDECIDED, MIN_NEGATIVE, MIN_NONFINITE,
+                  MIN_UNSETTLED, MIN_MAX_EVALS,
                   SCATT_LEGENDRE, SCATT_TABULAR, MAX_TAB_BINS, elastic_tab_batch, file6_tab_batch,
                   law9_tab_batch, scatt_nuclide_tab, scatt_library_tab, scatt_library_at, grid_error,
                   thin_segments, thin_bounded, lib_compare)

@@ -47,6 +47,7 @@ EXPORTS = [
     "ndpp_elastic_tab_batch", "ndpp_file6_tab_batch", "ndpp_law9_tab_batch", "ndpp_scatt_nuclide_tab",
     "ndpp_scatt_library_tab", "ndpp_scatt_library_at", "ndpp_grid_error",
     "ndpp_thin_segments", "ndpp_thin_bounded", "ndpp_lib_compare",
+    "ndpp_scatt_minimum", "ndpp_scatt_minimum_evals",
 ]
 
 
@@ -313,6 +314,20 @@ class Positivity(C.Structure):
     def as_dict(self) -> dict:
         return {k: getattr(self, k) for k, _ in self._fields_}
 
+
+class Minimum(C.Structure):
+    """ndpp_minimum: the summary of one ndpp_scatt_minimum call."""
+    _fields_ = [("rows", C.c_long), ("negative", C.c_long), ("undecided", C.c_long), ("nonfinite", C.c_long),
+                ("unsettled", C.c_long), ("min_hi", C.c_double), ("min_mu", C.c_double),
+                ("min_ein", C.c_int), ("min_group", C.c_int)]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+# ndpp_scatt_minimum: classes (low two bits of cls), the unsettled bit and the cap on evaluations per row
+MIN_POSITIVE, MIN_UNDECIDED, MIN_NEGATIVE, MIN_NONFINITE, MIN_UNSETTLED = 0, 1, 2, 3, 4
+MIN_MAX_EVALS = 16384
 
 FMT_ASCII, FMT_BINARY, FMT_HDF5, FMT_NONE, FMT_HUMAN = 1, 2, 3, 4, 5
 # per-E_in status bits (include/ndpp_hip.h NDPP_ST_*)
@@ -593,6 +608,11 @@ def load(build_if_missing: bool = False, torch_compat: bool | None = None) -> C.
                                           c_double_p, C.c_double, C.c_int, c_int_p, c_int_p, c_double_p]
         lib.ndpp_lib_compare.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, c_double_p, c_double_p, C.c_int,
                                          c_double_p, c_double_p, C.c_int, c_double_p, c_double_p, c_int_p, c_double_p]
+        lib.ndpp_scatt_minimum.argtypes = [C.c_int, C.c_int, C.c_int, c_double_p, C.c_int, C.c_double, c_double_p,
+                                           c_double_p, c_double_p, c_int_p, C.POINTER(Minimum)]
+        lib.ndpp_scatt_minimum_evals.argtypes = [C.c_int, C.c_int, C.c_int, c_double_p, C.c_int, C.c_double,
+                                                 c_double_p, c_double_p, c_double_p, c_int_p, c_int_p,
+                                                 C.POINTER(Minimum)]
     _lib = lib
     return lib
 
@@ -1133,6 +1153,32 @@ def scatt_positivity(mat, n_moments=None, mu_points=21, cap=None):
                                         _ip(rmu), C.byref(s)))
     m = min(cap, s.negative)
     return s, rows[:m].copy(), rmin[:m].copy(), rmu[:m].copy()
+
+
+def scatt_minimum(mat, n_moments=None, rel_tol=1e-10, want_evals=False):
+    """ndpp_scatt_minimum on one dense section mat[n_ein][G][L]: for every row ndpp_scatt_positivity
+    examines, a certified enclosure lo <= min over [-1, 1] of f <= hi = f(mu_at) (the rules are in
+    include/ndpp_hip.h).  n_moments: the first n_moments moments (default L); rel_tol: a row is
+    settled when hi - lo <= rel_tol * S + E.  Returns (Minimum summary, lo, hi, mu_at, cls), each
+    array (n_ein, G); cls is -1 outside the band, else MIN_POSITIVE / MIN_UNDECIDED / MIN_NEGATIVE /
+    MIN_NONFINITE in the low two bits plus MIN_UNSETTLED.  want_evals: also the evaluations of f each
+    row made, (n_ein, G) int32, as a sixth value."""
+    mat = _f64(mat)
+    if mat.ndim != 3:
+        raise ValueError(f"mat must be (n_ein, G, L), got shape {mat.shape}")
+    n, G, L = mat.shape
+    nm = L if n_moments is None else int(n_moments)
+    lo, hi, mu_at = np.zeros((n, G)), np.zeros((n, G)), np.zeros((n, G))
+    cls = np.full((n, G), -1, np.int32)
+    s = Minimum()
+    if want_evals:
+        evals = np.zeros((n, G), np.int32)
+        _check(load().ndpp_scatt_minimum_evals(n, G, L, _dp(mat), nm, float(rel_tol), _dp(lo), _dp(hi), _dp(mu_at),
+                                               _ip(cls), _ip(evals), C.byref(s)))
+        return s, lo, hi, mu_at, cls, evals
+    _check(load().ndpp_scatt_minimum(n, G, L, _dp(mat), nm, float(rel_tol), _dp(lo), _dp(hi), _dp(mu_at), _ip(cls),
+                                     C.byref(s)))
+    return s, lo, hi, mu_at, cls
 
 
 def expand_moments(moments, n_moments=None, mu_points=201):

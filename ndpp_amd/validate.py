@@ -18,6 +18,11 @@ Rules (tests/test_validate.py and tests/test_gpu_validate.py pin them):
 * Negative means !(f >= 0) at some grid point, so NaN moments are reported and never pass.
   min_value is the smallest non-NaN f (+inf if there is none).
 
+The sampled check is a sample, not a proof: a dip of f between two grid points passes it (at M = 21
+the spacing is 0.1, and f(mu) = (mu - 0.05)^2 - 1e-4 is +0.0024 at its smallest grid value).
+`minimum` is the check that cannot miss: per row a certified enclosure lo <= min f <= hi with the
+cosine attaining hi (ndpp_scatt_minimum), `--certified` on the command line.
+
 Deviations from the reference utilities, on purpose:
 
 * test_scatt_positivity reports (iE, g + gmin), which counts the band offset twice; the
@@ -29,7 +34,10 @@ Deviations from the reference utilities, on purpose:
 
 CLI: python -m ndpp_amd.validate <dir with ndpp_lib.xml> [--mu-points 21] [--moments N]
 [--json FILE]; exit 0 if every section is positive, 1 if any row is negative, 2 on an input
-error (or when the check cannot run: no device).
+error (or when the check cannot run: no device).  With --certified [--rel-tol 1e-10] the Legendre
+tables go through `minimum` (tabular ones keep tab_positivity): exit 1 if any row is negative or
+non-finite; undecided and unsettled rows are counted and printed and do not fail the run.
+--certified does not go together with --mu-points (exit 2).
 """
 from __future__ import annotations
 
@@ -192,6 +200,101 @@ def positivity(obj, mu_points: int = 21, n_moments=None) -> Report:
     return Report(out, int(mu_points), nm)
 
 
+@dataclass
+class MinimumSection:
+    """minimum() of one section: ndpp_minimum's fields and the first `cap` negative or non-finite rows."""
+    rows: int
+    negative: int
+    undecided: int
+    nonfinite: int
+    unsettled: int
+    min_hi: float
+    min_mu: float
+    min_ein: int
+    min_group: int
+    offending: list = field(default_factory=list)      # [(iE, g)] in (iE, g) order, 0-based
+    offending_hi: list = field(default_factory=list)    # the row's hi (NaN for a non-finite row)
+    offending_mu: list = field(default_factory=list)    # the cosine attaining it
+
+    @property
+    def positive(self) -> bool:
+        return self.negative == 0 and self.nonfinite == 0
+
+
+@dataclass
+class MinimumReport:
+    """minimum() of a table or result: one MinimumSection per scatter section present."""
+    sections: dict
+    n_moments: int
+    rel_tol: float
+
+    @property
+    def positive(self) -> bool:
+        return all(s.positive for s in self.sections.values())
+
+    @property
+    def min_hi(self) -> float:
+        return min((s.min_hi for s in self.sections.values()), default=math.inf)
+
+    @property
+    def offending(self) -> dict:
+        return {k: s.offending for k, s in self.sections.items()}
+
+    def as_dict(self) -> dict:
+        secs = {}
+        for k, s in self.sections.items():
+            d = asdict(s)
+            d["positive"] = s.positive
+            d["min_hi"] = _num(s.min_hi)
+            d["offending_hi"] = [_num(v) for v in s.offending_hi]
+            secs[k] = d
+        return {"certified": True, "positive": self.positive, "min_hi": _num(self.min_hi),
+                "n_moments": self.n_moments, "rel_tol": self.rel_tol, "sections": secs}
+
+
+def minimum(obj, n_moments=None, rel_tol: float = 1e-10, cap: int = 1000) -> MinimumReport:
+    """The certified positivity check on the GPU (ndpp_scatt_minimum): for every row `positivity`
+    examines, an enclosure lo <= min over [-1, 1] of f <= hi with the cosine attaining hi, so a row
+    reported positive IS positive and a negative one comes with a witness.  obj: what `positivity`
+    accepts.  Returns a MinimumReport; per section the counts (rows, negative, undecided: the minimum
+    is within the tolerance of zero, nonfinite, unsettled: the evaluation cap was reached), the
+    smallest hi with its cosine and row, and the first `cap` negative or non-finite rows with their
+    hi and mu_at."""
+    secs = _sections_of(obj)
+    L = max((m.shape[2] for m in secs.values()), default=0)
+    nm = L if n_moments is None else min(int(n_moments), L)
+    out = {}
+    for name, mat in secs.items():
+        s, _, hi, mu_at, cls = lib.scatt_minimum(mat, n_moments=min(nm, mat.shape[2]), rel_tol=float(rel_tol))
+        kind = cls & 3
+        bad = np.argwhere((cls >= 0) & ((kind == lib.MIN_NEGATIVE) | (kind == lib.MIN_NONFINITE)))[:int(cap)]
+        out[name] = MinimumSection(int(s.rows), int(s.negative), int(s.undecided), int(s.nonfinite),
+                                   int(s.unsettled), float(s.min_hi), float(s.min_mu), int(s.min_ein),
+                                   int(s.min_group), [(int(i), int(g)) for i, g in bad],
+                                   [float(hi[i, g]) for i, g in bad], [float(mu_at[i, g]) for i, g in bad])
+    return MinimumReport(out, nm, float(rel_tol))
+
+
+def minimum_reference(row, n_moments=None):
+    """Host reference of one row's minimum: (min over [-1, 1] of f, the cosine attaining it), from the
+    real roots of f' inside (-1, 1) (numpy.polynomial.legendre: legder, legroots) and both ends,
+    evaluated with legval; the first cosine in ascending order on a tie."""
+    from numpy.polynomial import legendre as leg
+    a = np.asarray(row, dtype=np.float64)
+    nm = len(a) if n_moments is None else min(int(n_moments), len(a))
+    c = (np.arange(nm) + 0.5) * a[:nm]
+    cand = [-1.0, 1.0]
+    d = np.trim_zeros(leg.legder(c), "b") if nm > 1 else np.zeros(0)
+    if len(d) > 1:
+        r = leg.legroots(d)
+        r = r[np.abs(r.imag) <= 1e-9 * np.maximum(1.0, np.abs(r.real))].real if np.iscomplexobj(r) else r
+        cand += [float(x) for x in r if -1.0 < x < 1.0]
+    cand = np.array(sorted(cand))
+    f = leg.legval(cand, c)
+    k = int(np.argmin(f))
+    return float(f[k]), float(cand[k])
+
+
 def read_library(directory) -> list:
     """[(table attributes, NdppTable)] of every table ndpp_lib.xml lists, read with reader.py
     (BINARY or ASCII per <filetype>); paths are relative to the directory of ndpp_lib.xml."""
@@ -229,6 +332,22 @@ def _print_report(name: str, t: reader.NdppTable, rep: Report, out) -> None:
             print(f"      ... {s.negative - 10} more", file=out)
 
 
+def _print_minimum(name: str, t: reader.NdppTable, rep: MinimumReport, out) -> None:
+    status = "positive" if rep.positive else "NEGATIVE"
+    print(f"{name}: {status}  (P{t.scatt_order}, {t.groups} groups, {rep.n_moments} moments, certified, "
+          f"rel tol {rep.rel_tol:g})", file=out)
+    for sec, s in rep.sections.items():
+        where = (f" at mu = {s.min_mu: .6f}, E_in {s.min_ein + 1}, group {s.min_group + 1}" if s.min_group >= 0 else
+                 (f" at E_in {s.min_ein + 1} (all-zero)" if s.min_ein >= 0 else ""))
+        print(f"  {sec:12s} rows {s.rows:7d}  negative {s.negative:7d}  non-finite {s.nonfinite:7d}  "
+              f"undecided {s.undecided:7d}  unsettled {s.unsettled:7d}  min {s.min_hi: .6e}{where}", file=out)
+        for (iE, g), v, mu in list(zip(s.offending, s.offending_hi, s.offending_mu))[:10]:
+            what = "non-finite moments" if math.isnan(v) else f"f = {v: .6e} at mu = {mu: .6f}"
+            print(f"      E_in {iE + 1:6d} ({_ein(t, sec, iE):.6e} MeV)  group {g + 1:4d}  {what}", file=out)
+        if s.negative + s.nonfinite > 10:
+            print(f"      ... {s.negative + s.nonfinite - 10} more", file=out)
+
+
 def _ein(t: reader.NdppTable, sec: str, iE: int) -> float:
     return float(getattr(t, sec).ein[iE])
 
@@ -239,10 +358,29 @@ def main(argv=None) -> int:
                                              "Legendre expansions (exit 0: all positive, 1: negative rows, "
                                              "2: input error or no device).")
     ap.add_argument("library", help="directory holding ndpp_lib.xml (or the xml file itself)")
-    ap.add_argument("--mu-points", type=int, default=21, help="points of linspace(-1, 1, M) (default 21)")
+    ap.add_argument("--mu-points", type=int, default=None, help="points of linspace(-1, 1, M) (default 21)")
     ap.add_argument("--moments", type=int, default=None, help="moments to sum (default: all, scatt_order + 1)")
     ap.add_argument("--json", default=None, help="write the full report to this file")
+    ap.add_argument("--certified", action="store_true",
+                    help="enclose every row's true minimum instead of sampling a grid (not with --mu-points); "
+                         "exit 1 if any row is negative or non-finite")
+    ap.add_argument("--rel-tol", type=float, default=None,
+                    help="with --certified: width of a settled enclosure relative to sum (l + 1/2)|a_l| "
+                         "(default 1e-10)")
     a = ap.parse_args(argv)
+    if a.certified and a.mu_points is not None:
+        print("validate: --certified examines the whole interval; it does not go together with --mu-points",
+              file=sys.stderr)
+        return 2
+    if a.rel_tol is not None and not a.certified:
+        print("validate: --rel-tol needs --certified", file=sys.stderr)
+        return 2
+    if a.rel_tol is not None and not (a.rel_tol >= 0.0 and math.isfinite(a.rel_tol)):
+        print("validate: --rel-tol must be a finite value >= 0", file=sys.stderr)
+        return 2
+    rel_tol = 1e-10 if a.rel_tol is None else a.rel_tol
+    if a.mu_points is None:
+        a.mu_points = 21
     if a.mu_points < 1 or (a.moments is not None and a.moments < 1):
         print("validate: --mu-points and --moments must be at least 1", file=sys.stderr)
         return 2
@@ -255,19 +393,29 @@ def main(argv=None) -> int:
     for attrs, t in tables:
         name = attrs.get("name", t.name)
         try:
-            rep = (tab_positivity(t) if t.scatt_type == reader.SCATT_TYPE_TABULAR else
-                   positivity(t, mu_points=a.mu_points, n_moments=a.moments))
+            if t.scatt_type == reader.SCATT_TYPE_TABULAR:
+                rep = tab_positivity(t)
+            elif a.certified:
+                rep = minimum(t, n_moments=a.moments, rel_tol=rel_tol)
+            else:
+                rep = positivity(t, mu_points=a.mu_points, n_moments=a.moments)
         except lib.NdppError as e:
             print(f"validate: {name}: {e}", file=sys.stderr)
             return 2
-        _print_report(name, t, rep, sys.stdout)
+        if isinstance(rep, MinimumReport):
+            _print_minimum(name, t, rep, sys.stdout)
+        else:
+            _print_report(name, t, rep, sys.stdout)
         full[name] = dict(rep.as_dict(), path=attrs.get("path"))
         if not rep.positive:
             bad.append(name)
-    print(f"{len(tables)} tables, {len(bad)} with negative rows" + (": " + ", ".join(bad) if bad else ""))
+    print(f"{len(tables)} tables, {len(bad)} with negative" + (" or non-finite" if a.certified else "") + " rows"
+          + (": " + ", ".join(bad) if bad else ""))
     if a.json:
-        Path(a.json).write_text(json.dumps({"library": str(a.library), "positive": not bad, "tables": full},
-                                           indent=1) + "\n")
+        head = {"library": str(a.library), "positive": not bad}
+        if a.certified:
+            head.update(certified=True, rel_tol=rel_tol)
+        Path(a.json).write_text(json.dumps(dict(head, tables=full), indent=1) + "\n")
     return 1 if bad else 0
 
 
