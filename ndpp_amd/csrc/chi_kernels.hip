@@ -381,6 +381,12 @@ extern "C" int ndpp_chi_batch(const ndpp_chi_nuclide* nuc, int n_prompt,
     return fail(NDPP_EINVAL, "NULL array argument");
   if (nuc->n_grid < 2 || !nuc->energy || !nuc->fission || !nuc->nu_t_data)
     return fail(NDPP_EINVAL, "nuclide grid / nu data missing");
+  // chi_prob steps j past a duplicated pair (chidata_header.F90:197-199); with Ein at or above the
+  // last energy j is n_grid - 1, and a pair there makes it read fission(n_grid + 1) and one sigma
+  // past its end (the reference reads out of bounds)
+  if (nuc->energy[nuc->n_grid - 2] == nuc->energy[nuc->n_grid - 1])
+    return fail(NDPP_EINVAL, "nuclide energy grid: the last two of its %d points are equal (%g)", nuc->n_grid,
+                nuc->energy[nuc->n_grid - 1]);
   if (nuc->nu_t_type != NU_POLYNOMIAL && nuc->nu_t_type != NU_TABULAR)
     return fail(NDPP_EINVAL, "no neutron emission data (nu_t_type=%d)", nuc->nu_t_type);  // fission.F90:27
   if (nuc->nu_t_type == NU_POLYNOMIAL) {

@@ -395,10 +395,43 @@ contains
     integer(c_int), intent(out) :: nE
     real(c_double), intent(out) :: E_grid(ncap), chi_t(nb - 1, ncap), chi_p(nb - 1, ncap)
     real(c_double), intent(out) :: chi_d(nb - 1, ncap, max(n_prec, 1))
+    integer(c_int), allocatable :: zero(:)
+    integer(c_int) :: none_i(1)
+    real(c_double) :: none_r(1)
+    allocate(zero(sum(nnest(1:n_rxn))))
+    zero = 0
+    call ref_calc_chi_pv(n_grid, energy, fission_xs, nu_t_type, n_nu_t, nu_t_data, &
+                         nu_d_type, n_nu_d, nu_d_data, n_prec, n_pd, prec_data, &
+                         n_rxn, mts, thr, sigptr, sig, nnest, law, sptr, sdata, &
+                         zero, none_i, none_i, zero, none_r, none_r, &
+                         dlaw, dptr, ddata, e_bins, nb, ncap, nE, E_grid, chi_t, chi_p, chi_d)
+  end subroutine ref_calc_chi
+
+  ! The same with a law-validity table (edist % p_valid) per prompt spectrum: spectrum s has
+  ! pv_nr(s) regions and pv_np(s) pairs; pv_nbt / pv_int hold the regions and pv_x / pv_y the
+  ! pairs of all spectra one after the other, in spectrum order.  pv_nr(s) = 0 with pv_np(s) > 0
+  ! is a table with pairs but no regions (chidata_header.F90:210 then ignores it).
+  subroutine ref_calc_chi_pv(n_grid, energy, fission_xs, nu_t_type, n_nu_t, nu_t_data, &
+                             nu_d_type, n_nu_d, nu_d_data, n_prec, n_pd, prec_data, &
+                             n_rxn, mts, thr, sigptr, sig, nnest, law, sptr, sdata, &
+                             pv_nr, pv_nbt, pv_int, pv_np, pv_x, pv_y, &
+                             dlaw, dptr, ddata, e_bins, nb, ncap, nE, E_grid, chi_t, chi_p, chi_d) &
+      bind(C, name="ref_calc_chi_pv")
+    integer(c_int), value :: n_grid, nu_t_type, n_nu_t, nu_d_type, n_nu_d, n_prec, n_pd
+    integer(c_int), value :: n_rxn, nb, ncap
+    real(c_double), intent(in) :: energy(n_grid), fission_xs(n_grid), nu_t_data(*), nu_d_data(*)
+    real(c_double), intent(in) :: prec_data(*), sig(*), sdata(*), ddata(*), e_bins(nb)
+    integer(c_int), intent(in) :: mts(*), thr(*), sigptr(*), nnest(*), law(*), sptr(*), dlaw(*), dptr(*)
+    integer(c_int), intent(in) :: pv_nr(*), pv_nbt(*), pv_int(*), pv_np(*)
+    real(c_double), intent(in) :: pv_x(*), pv_y(*)
+    integer(c_int), intent(out) :: nE
+    real(c_double), intent(out) :: E_grid(ncap), chi_t(nb - 1, ncap), chi_p(nb - 1, ncap)
+    real(c_double), intent(out) :: chi_d(nb - 1, ncap, max(n_prec, 1))
     type(Nuclide), pointer :: nuc
     type(DistEnergy), pointer :: ed, prev
     real(8), allocatable :: Eg(:), ct(:,:), cp(:,:), cd(:,:,:)
-    integer :: r, s, k, j
+    integer :: r, s, k, j, ir, ip
+    ir = 0; ip = 0
     allocate(nuc)
     nuc % name = 'fiss.00c'; nuc % awr = 233.0_8; nuc % kT = 2.53E-8_8
     nuc % n_grid = n_grid
@@ -429,8 +462,20 @@ contains
         ed % law = law(s)
         allocate(ed % data(sptr(s + 1) - sptr(s)))
         ed % data = sdata(sptr(s) + 1 : sptr(s + 1))
-        ed % p_valid % n_regions = 0
-        ed % p_valid % n_pairs = 0
+        ed % p_valid % n_regions = pv_nr(s)
+        ed % p_valid % n_pairs = pv_np(s)
+        if (pv_nr(s) > 0) then
+          allocate(ed % p_valid % nbt(pv_nr(s)), ed % p_valid % int(pv_nr(s)))
+          ed % p_valid % nbt = pv_nbt(ir + 1 : ir + pv_nr(s))
+          ed % p_valid % int = pv_int(ir + 1 : ir + pv_nr(s))
+          ir = ir + pv_nr(s)
+        end if
+        if (pv_np(s) > 0) then
+          allocate(ed % p_valid % x(pv_np(s)), ed % p_valid % y(pv_np(s)))
+          ed % p_valid % x = pv_x(ip + 1 : ip + pv_np(s))
+          ed % p_valid % y = pv_y(ip + 1 : ip + pv_np(s))
+          ip = ip + pv_np(s)
+        end if
         if (k == 1) then
           nuc % reactions(r) % edist => ed
         else
@@ -455,7 +500,7 @@ contains
       chi_p(:, 1:nE) = cp
       if (n_prec > 0) chi_d(:, 1:nE, 1:n_prec) = cd
     end if
-  end subroutine ref_calc_chi
+  end subroutine ref_calc_chi_pv
 
   ! ScattData%init (scattdata_header.F90:78) + %convert_distro (:325) on an
   ! in-memory reaction: MT, optional angular distribution (has_adist), optional

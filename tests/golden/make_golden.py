@@ -202,13 +202,12 @@ def sab_goldens(R):
     np.savez_compressed(HERE / "sab.npz", **out)
 
 
-def chi_goldens(R):
-    """calc_chi (chi.F90:21-169) through the reference on the synthetic fissionable
-    nuclide of tests/synth.chi_case."""
-    sys.path.insert(0, str(HERE.parent))
-    from synth import chi_case
+def ref_chi_case(R, c, ncap=64, entry="ref_calc_chi_pv"):
+    """calc_chi (chi.F90:21-169) through the reference on one case dict in the layout of
+    tests/synth.chi_case (entries of `spectra` may carry a p_valid dict, as chi_structs reads
+    them).  entry "ref_calc_chi" is the shim's first signature, without p_valid tables.
+    Returns e_grid[NE], chi_t[NE][G], chi_p[NE][G], chi_d[n_prec][NE][G]."""
     pi = C.POINTER(i)
-    c = chi_case()
     keep = []
 
     def arr(a, dt=np.float64):
@@ -217,27 +216,65 @@ def chi_goldens(R):
         return a
 
     cum = lambda xs: np.cumsum([0] + [len(x) for x in xs]).astype(np.int32)
-    sig, spec, dly = c["sig"], [x for _, x in c["spectra"]], [x for _, x in c["delayed"]]
+    cat = lambda xs: np.concatenate(xs) if len(xs) else np.zeros(1)
+    sig, spec, dly = c["sig"], [e[1] for e in c["spectra"]], [e[1] for e in c["delayed"]]
     bins = arr(c["bins"])
     G = len(bins) - 1
-    R.ref_calc_chi.argtypes = [i, P, P, i, i, P, i, i, P, i, i, P, i, pi, pi, pi, P, pi, pi, pi, P,
-                               pi, pi, P, P, i, i, pi, P, P, P, P]
-    ncap = 64
     nE = C.c_int()
     Eg, ct, cp = np.zeros(ncap), np.zeros((ncap, G)), np.zeros((ncap, G))
-    cd = np.zeros((c["n_prec"], ncap, G))
+    cd = np.zeros((max(c["n_prec"], 1), ncap, G))
     i32 = lambda a: arr(a, np.int32).ctypes.data_as(pi)
-    R.ref_calc_chi(c["n_grid"], dp(arr(c["energy"])), dp(arr(c["fission"])), c["nu_t_type"],
-                   len(c["nu_t_data"]), dp(arr(c["nu_t_data"])), c["nu_d_type"], len(c["nu_d_data"]),
-                   dp(arr(c["nu_d_data"])), c["n_prec"], len(c["prec_data"]), dp(arr(c["prec_data"])),
-                   len(c["mts"]), i32(c["mts"]), i32(c["thr"]), i32(cum(sig)),
-                   dp(arr(np.concatenate(sig))), i32(c["nnest"]), i32([l for l, _ in c["spectra"]]),
-                   i32(cum(spec)), dp(arr(np.concatenate(spec))), i32([l for l, _ in c["delayed"]]),
-                   i32(cum(dly)), dp(arr(np.concatenate(dly))), dp(bins), G + 1, ncap,
-                   C.byref(nE), dp(Eg), dp(ct), dp(cp), dp(cd))
+    head = [c["n_grid"], dp(arr(c["energy"])), dp(arr(c["fission"])), c["nu_t_type"],
+            len(c["nu_t_data"]), dp(arr(c["nu_t_data"])), c["nu_d_type"], len(c["nu_d_data"]),
+            dp(arr(c["nu_d_data"])), c["n_prec"], len(c["prec_data"]), dp(arr(c["prec_data"])),
+            len(c["mts"]), i32(c["mts"]), i32(c["thr"]), i32(cum(sig)),
+            dp(arr(np.concatenate(sig))), i32(c["nnest"]), i32([e[0] for e in c["spectra"]]),
+            i32(cum(spec)), dp(arr(np.concatenate(spec)))]
+    tail = [i32([e[0] for e in c["delayed"]] or [0]), i32(cum(dly)), dp(arr(cat(dly))), dp(bins), G + 1, ncap,
+            C.byref(nE), dp(Eg), dp(ct), dp(cp), dp(cd)]
+    t_head = [i, P, P, i, i, P, i, i, P, i, i, P, i, pi, pi, pi, P, pi, pi, pi, P]
+    t_tail = [pi, pi, P, P, i, i, pi, P, P, P, P]
+    pvs = [(e[2] if len(e) > 2 and e[2] is not None else {}) for e in c["spectra"]]
+    if entry == "ref_calc_chi":
+        assert not any(pvs)
+        R.ref_calc_chi.argtypes = t_head + t_tail
+        R.ref_calc_chi(*head, *tail)
+    else:
+        nbt = [list(v.get("pv_nbt") or []) for v in pvs]
+        itp = [list(v.get("pv_int") or []) for v in pvs]
+        px = [list(v.get("pv_x") if v.get("pv_x") is not None else []) for v in pvs]
+        py = [list(v.get("pv_y") if v.get("pv_y") is not None else []) for v in pvs]
+        flat = lambda xs: [v for x in xs for v in x] or [0]
+        R.ref_calc_chi_pv.argtypes = t_head + [pi, pi, pi, pi, P, P] + t_tail
+        R.ref_calc_chi_pv(*head, i32([len(x) for x in nbt]), i32(flat(nbt)), i32(flat(itp)),
+                          i32([len(x) for x in px]), dp(arr(flat(px))), dp(arr(flat(py))), *tail)
     n = nE.value
-    np.savez_compressed(HERE / "chi.npz", e_grid=Eg[:n].copy(), chi_t=ct[:n].copy(),
-                        chi_p=cp[:n].copy(), chi_d=cd[:, :n].copy())
+    assert 0 < n <= ncap, (n, ncap)
+    return Eg[:n].copy(), ct[:n].copy(), cp[:n].copy(), cd[:c["n_prec"], :n].copy()
+
+
+def chi_goldens(R, out=None):
+    """calc_chi (chi.F90:21-169) through the reference on the synthetic fissionable
+    nuclide of tests/synth.chi_case."""
+    sys.path.insert(0, str(HERE.parent))
+    from synth import chi_case
+    Eg, ct, cp, cd = ref_chi_case(R, chi_case(), entry="ref_calc_chi")
+    np.savez_compressed(out or HERE / "chi.npz", e_grid=Eg, chi_t=ct, chi_p=cp, chi_d=cd)
+
+
+def chi_edge_goldens(R, out=None):
+    """calc_chi through the reference on every case of tests/synth.chi_edge_cases: the laws, TAB1
+    schemes, thresholds and table edges that chi_case does not reach.  <case>_e_grid, _chi_t,
+    _chi_p, _chi_d per case."""
+    sys.path.insert(0, str(HERE.parent))
+    from synth import chi_edge_cases
+    res = {}
+    for name, c in chi_edge_cases().items():
+        Eg, ct, cp, cd = ref_chi_case(R, c, ncap=160)
+        res.update({f"{name}_e_grid": Eg, f"{name}_chi_t": ct, f"{name}_chi_p": cp, f"{name}_chi_d": cd})
+        print(f"chi_edges: {name}: {len(Eg)} incoming energies, G = {ct.shape[1]}, "
+              f"{int(np.isnan(ct).any(axis=1).sum())} rows of chi_t with NaN")
+    np.savez_compressed(out or HERE / "chi_edges.npz", **res)
 
 
 def ref_create_ein_grid(R, c, cap=200000):
@@ -777,6 +814,7 @@ def main():
     file6_goldens(R)
     sab_goldens(R)
     chi_goldens(R)
+    chi_edge_goldens(R)
 
     # ---- scalar helpers: calc_pn, find_FG_mu, tolab
     xs = np.concatenate([np.linspace(-1, 1, 41), rng.uniform(-1, 1, 60)])
@@ -812,6 +850,8 @@ if __name__ == "__main__":
         library_goldens(load_ref())
     elif len(sys.argv) > 1 and sys.argv[1] == "file4_edges":
         file4_edge_goldens(load_ref())
+    elif len(sys.argv) > 1 and sys.argv[1] == "chi_edges":
+        chi_edge_goldens(load_ref())
     elif len(sys.argv) > 1 and sys.argv[1] == "tunables":
         tunables_goldens(load_ref())
     else:

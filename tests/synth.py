@@ -177,6 +177,324 @@ def chi_case(seed=18):
                 bins=np.concatenate([[0.0], np.logspace(-3, np.log10(20.0), 7)]))
 
 
+# ---- chi edge cases (tests/golden/chi_edges.npz) ------------------------------------------------
+# Every number below comes from literals, + - * /, sqrt, seeded uniform draws and np.linspace:
+# no np.exp / np.log / np.logspace, whose last bits depend on the numpy build, because the
+# goldens are compared bit for bit with inputs regenerated on another machine.
+def tab1_regions(x, y, nbt=(), ints=()):
+    """A TAB1 block with interpolation regions: NR, NBT(NR), INT(NR), NE, x(NE), y(NE).  The last
+    NBT is the point count, so that interpolation.F90:84-91 never leaves `interp` unset."""
+    assert len(nbt) == len(ints) and len(x) == len(y) and (len(nbt) == 0 or nbt[-1] == len(x))
+    return ([float(len(nbt))] + [float(b) for b in nbt] + [float(s) for s in ints] + [float(len(x))] +
+            [float(v) for v in x] + [float(v) for v in y])
+
+
+def tab1_parse(block):
+    """(nbt, ints, x, y) of the TAB1 block that starts at block[0]."""
+    block = np.asarray(block, dtype=np.float64)
+    NR = int(block[0])
+    NE = int(block[1 + 2 * NR])
+    o = 2 + 2 * NR
+    return (block[1:1 + NR].astype(int), block[1 + NR:1 + 2 * NR].astype(int), block[o:o + NE],
+            block[o + NE:o + 2 * NE])
+
+
+def law4_rows(e_in, eouts, widths, scheme=None):
+    """law4_block with every row's outgoing grid given: eouts[k] are the E_out points of incoming
+    energy k, its pdf is (E + 1e-3) / (1 + E / widths[k])^3, the cdf its trapezoid sums, both
+    normalised.  scheme None: NR = 0; else NR = 1, NBT = NE, INT = scheme."""
+    NE = len(e_in)
+    assert len(eouts) == NE and len(widths) == NE
+    head = ([1.0, float(NE), float(scheme)] if scheme is not None else [0.0]) + [float(NE)] + [float(e) for e in e_in]
+    blocks, locs = [], []
+    pos = len(head) + NE
+    for eo, w in zip(eouts, widths):
+        eo = np.asarray(eo, dtype=np.float64)
+        q = 1.0 + eo / w
+        pdf = (eo + 1e-3) / (q * q * q)
+        cdf = np.concatenate([[0.0], np.cumsum(0.5 * (pdf[1:] + pdf[:-1]) * np.diff(eo))])
+        pdf, cdf = pdf / cdf[-1], cdf / cdf[-1]
+        blk = [2.0, float(len(eo))] + list(eo) + list(pdf) + list(cdf)
+        locs.append(float(pos))
+        pos += len(blk)
+        blocks += blk
+    return np.array(head + locs + blocks)
+
+
+def law4_table_rows(data):
+    """[(E_in, E_out(NP), cdf(NP))] of a law-4 / law-61 block (for checks on the inputs)."""
+    data = np.asarray(data)
+    NR = int(data[0])
+    NE = int(data[1 + 2 * NR])
+    o = 2 + 2 * NR
+    rows = []
+    for k in range(NE):
+        lc = int(data[o + NE + k])
+        NP = int(data[lc + 1])
+        rows.append((data[o + k], data[lc + 2:lc + 2 + NP], data[lc + 2 + 2 * NP:lc + 2 + 3 * NP]))
+    return rows
+
+
+def _rand_rows(seed, n_rows, n_pts, e_max, w0=0.4, dw=0.9):
+    rng = np.random.default_rng(seed)
+    eouts = [np.concatenate([[0.0], np.sort(rng.uniform(0, e_max, n_pts - 2)), [e_max]]) for _ in range(n_rows)]
+    return eouts, [w0 + dw * k for k in range(n_rows)]
+
+
+def _law4(e_in, seed, n_pts=9, e_max=15.0, scheme=None, **kw):
+    return law4_rows(e_in, *_rand_rows(seed, len(e_in), n_pts, e_max, **kw), scheme=scheme)
+
+
+def chi_spectrum_grid(data):
+    """incoming energies of one spectrum: chi_init, chidata_header.F90:98-108"""
+    NR = int(data[0])
+    NE = int(data[1 + 2 * NR])
+    return np.asarray(data[2 + 2 * NR:2 + 2 * NR + NE], dtype=np.float64)
+
+
+def chi_union_grid(c):
+    """The union of the spectra's incoming grids, the energies calc_chi evaluates at (chi.F90:97-113;
+    none of the edge cases has a zero energy or a tail the reference's merge would drop)."""
+    return np.unique(np.concatenate([chi_spectrum_grid(e[1]) for e in c["spectra"] + c["delayed"]]))
+
+
+def _geom(e0, ratio, n, last=None):
+    """e0 * ratio^k by repeated multiplication (np.logspace goes through pow), optionally ending at `last`"""
+    e = e0 * np.cumprod(np.concatenate([[1.0], np.full(n - 1, float(ratio))]))
+    if last is not None:
+        assert e[-2] < last
+        e[-1] = last
+    return e
+
+
+NUC_E = _geom(1e-11, 1.78, 50, last=20.0)
+CHI_BINS7 = np.array([0.0, 1e-3, 5e-3, 0.03, 0.15, 0.75, 4.0, 20.0])
+NU_T_POLY = np.array([4.0, 2.4, 0.12, 1e-3, -2e-5])          # NC = 4: E**0 .. E**3
+
+
+def _chi_assemble(energy, rxns, delayed, yields, bins, why, arith=False, nu_t=(1, NU_T_POLY), nu_d=None):
+    """A chi_case()-shaped dict.  rxns: (MT, threshold, amplitude, [spectrum entries]) per fission
+    reaction, its sigma amplitude * (1 + 0.2 sqrt(E)) from the threshold on, ramped from 0.1 to 1
+    when the threshold is above 1; fission = 0.05 + the sum, so that it is positive everywhere.
+    delayed: one spectrum entry per precursor group; yields: its TAB1 yield block.  `why` states the
+    condition the case exists for, `arith` that no spectrum or TAB1 block of it reaches
+    exp / log / erf / sinh (the kernel must then equal the Fortran bit for bit)."""
+    energy = np.asarray(energy, dtype=np.float64)
+    n = len(energy)
+    shape = 1.0 + 0.2 * np.sqrt(energy)
+    fission = np.full(n, 0.05)
+    sig, spectra = [], []
+    for _, thr, amp, specs in rxns:
+        ramp = np.ones(n - thr + 1) if thr == 1 else np.linspace(0.1, 1.0, n - thr + 1)
+        s = amp * shape[thr - 1:] * ramp
+        fission[thr - 1:] += s
+        sig.append(s)
+        spectra += list(specs)
+    prec = []
+    for j, yb in enumerate(yields):
+        prec += [0.01 * (j + 1)] + list(yb)
+    if nu_d is None:
+        nu_d = (2, tab1_block([1e-11, 4.0, 20.0], [0.016, 0.016, 0.009])) if delayed else (0, [0.0])
+    assert len(yields) == len(delayed)
+    return dict(n_grid=n, energy=energy, fission=fission, nu_t_type=nu_t[0], nu_t_data=np.array(nu_t[1], dtype=np.float64),
+                nu_d_type=nu_d[0], nu_d_data=np.array(nu_d[1], dtype=np.float64), n_prec=len(delayed),
+                prec_data=np.array(prec if prec else [0.0]), mts=[r[0] for r in rxns], thr=[r[1] for r in rxns],
+                sig=sig, nnest=[len(r[3]) for r in rxns], spectra=spectra, delayed=list(delayed),
+                bins=np.asarray(bins, dtype=np.float64), why=why, arith=arith)
+
+
+def _lin_yields(n):
+    return [tab1_block([1e-11, 20.0], [0.2 + 0.1 * j, 0.25 + 0.1 * j]) for j in range(n)]
+
+
+def _arr(*parts):
+    return np.array([float(v) for p in parts for v in p])
+
+
+def _case_arith_only():
+    eA, eB, eC = [1e-11, 1e-3, 1.0, 9.0, 20.0], [1e-11, 3e-2, 14.0, 20.0], [1e-11, 2e-6, 0.4, 20.0]
+    rxns = [(19, 1, 2.0, [(4, _law4(eA, 401)), (61, _law4(eB, 402, scheme=1))]),   # law 61, NR=1 INT=1: NOT a histogram
+            (20, 30, 0.6, [(4, _law4(eC, 403, scheme=1))])]                        # law 4, NR=1 INT=1: histogram
+    delayed = [(61, _law4([1e-11, 5e-5, 20.0], 404, n_pts=7, e_max=3.0)),
+               (4, _law4([1e-11, 2.0, 20.0], 405, n_pts=7, e_max=2.0, scheme=1))]
+    return _chi_assemble(NUC_E, rxns, delayed, _lin_yields(2), CHI_BINS7, arith=True,
+                         why="laws 4 and 61 only, a law-4 histogram table, a law-61 table with NR=1 INT=1 that has "
+                             "incoming energies at x > 0.5; polynomial nu_t, lin-lin nu_d and yields")
+
+
+def _case_tab1_schemes():
+    T7 = tab1_regions([1e-11, 1e-8, 1e-5, 1e-3, 0.1, 1.0, 5.0, 20.0], [1.3, 1.25, 1.32, 1.4, 1.36, 1.45, 1.5, 1.6],
+                      [3, 5, 8], [5, 2, 4])
+    T9 = tab1_regions([1e-11, 3e-7, 2e-4, 0.03, 2.0, 20.0], [1.0, 1.1, 1.25, 1.4, 1.7, 2.0], [6], [1])
+    Wa = tab1_regions([1e-11, 3.5, 5.0, 8.0, 12.0, 20.0], [0.95, 0.97, 1.0, 1.02, 1.04, 1.05], [6], [3])
+    Wb = tab1_regions([1e-11, 4.2, 6.0, 10.0, 20.0], [2.2, 2.3, 2.45, 2.5, 2.6], [5], [4])
+    rxns = [(19, 1, 2.0, [(7, _arr(T7, [-20.0]))]), (20, 1, 0.6, [(9, _arr(T9, [-5.0]))]),
+            (21, 1, 0.3, [(11, _arr(Wa, Wb, [3.0]))])]
+    delayed = [(7, _arr(tab1_block([1e-11, 5e-10, 7e-4, 20.0], [0.4, 0.41, 0.43, 0.45]), [-20.0])),
+               (7, _arr(tab1_block([1e-11, 6e-6, 0.5, 20.0], [0.5, 0.52, 0.55, 0.6]), [-20.0])),
+               (7, _arr(tab1_block([1e-11, 4e-2, 7.0, 20.0], [0.3, 0.32, 0.33, 0.36]), [-20.0]))]
+    yields = [tab1_block([1e-11, 1e-3, 20.0], [0.2, 0.22, 0.25]),
+              tab1_regions([1e-11, 1e-5, 1.0, 20.0], [0.3, 0.28, 0.35, 0.31], [4], [2]),
+              tab1_regions([1e-11, 1e-9, 1e-6, 1e-4, 0.02, 3.0, 20.0], [0.4, 0.45, 0.42, 0.5, 0.47, 0.44, 0.4],
+                           [3, 5, 7], [2, 4, 1])]
+    nu_t = (2, tab1_regions([1e-11, 1e-7, 1e-2, 4.0, 20.0], [2.4, 2.41, 2.5, 2.9, 4.8], [5], [5]))
+    nu_d = (2, tab1_regions([1e-11, 1e-9, 1e-6, 1e-4, 0.05, 2.5, 9.0, 20.0],
+                            [0.016, 0.0162, 0.0158, 0.016, 0.0155, 0.014, 0.011, 0.009], [2, 5, 8], [1, 3, 5]))
+    return _chi_assemble(NUC_E, rxns, delayed, yields, CHI_BINS7, nu_t=nu_t, nu_d=nu_d,
+                         why="TAB1 blocks with NR=0, NR=1 with INT 1..5 and NR=3 with mixed schemes: T(E) of laws 7 "
+                             "and 9, a(E), b(E) of law 11, tabular nu_t, nu_d and the yields; union energies "
+                             "strictly inside a bin of every region")
+
+
+def _case_thresholds():
+    T7 = tab1_block([1e-5, 1e-3, 0.2, 0.5, 0.9, 3.0, 20.0], [1.2, 1.22, 1.25, 1.3, 1.33, 1.4, 1.5])
+    T9 = tab1_block([1e-5, 0.05, 1.0, 2.0, 2.6, 7.0, 20.0], [0.8, 0.82, 0.9, 1.0, 1.05, 1.2, 1.4])
+    Wa = tab1_block([1e-5, 1.7, 3.0, 4.5, 11.0, 20.0], [0.95, 0.96, 0.98, 1.0, 1.03, 1.05])
+    Wb = tab1_block([1e-5, 20.0], [2.2, 2.6])
+    # law 7 at Ein = 3: Ein - U = 2.5 exactly, a group edge (the clamp's `>` is strict)
+    rxns = [(18, 3, 1.0, [(4, _law4([1e-5, 1e-4, 0.01, 6.5, 20.0], 411))]),          # MT 18: sigma is `fission`
+            (19, 30, 1.5, [(7, _arr(T7, [0.5]))]), (20, 38, 0.6, [(9, _arr(T9, [2.0]))]),
+            (21, 44, 0.3, [(11, _arr(Wa, Wb, [3.0]))])]
+    delayed = [(9, _arr(tab1_block([1e-5, 0.6, 1.0, 1.3, 20.0], [0.4, 0.42, 0.44, 0.45, 0.5]), [1.0])),
+               (4, _law4([1e-5, 0.3, 20.0], 412, n_pts=7, e_max=3.0))]
+    return _chi_assemble(NUC_E, rxns, delayed, _lin_yields(2), [0.0, 1e-3, 0.1, 0.3, 1.0, 2.5, 6.0, 20.0],
+                         why="U > 0 inside the grid for laws 7, 9, 11: at least two union energies with Ein - U <= 0 "
+                             "and several above per law, group edges on both sides of Ein - U and of U; thresholds "
+                             "> 1 with union energies on both sides; one reaction on MT 18")
+
+
+def _ulps(v, n):
+    for _ in range(abs(n)):
+        v = np.nextafter(v, np.inf if n > 0 else -np.inf)
+    return float(v)
+
+
+def _case_nearest_row():
+    e1 = [1e-11, 1.0, 3.0, 15.0, 20.0]                                   # x = 0.5 of its row [1, 3] is E = 2
+    e2 = [1e-11, _ulps(2.0, -3), _ulps(2.0, -1), 2.0, _ulps(2.0, 1), _ulps(2.0, 3), 20.0]
+    eo1, _ = _rand_rows(421, len(e1), 10, 15.0)
+    rxns = [(19, 1, 2.0, [(4, law4_rows(e1, eo1, [0.3, 0.6, 2.5, 5.0, 8.0]))]),
+            (20, 1, 0.7, [(4, _law4(e2, 422, scheme=1, dw=0.5))])]
+    delayed = [(4, _law4([1e-11, 20.0], 423, n_pts=7, e_max=3.0))]
+    return _chi_assemble(NUC_E, rxns, delayed, _lin_yields(1), CHI_BINS7, arith=True,
+                         why="the nearest-row rule `x > 0.5` of a non-histogram law-4 table at x = 0.5 exactly and "
+                             "within a few ulp on either side, rows that differ by more than 1e-3 in a group; the "
+                             "second table is a histogram one with an incoming energy at x > 0.5")
+
+
+def _case_eout_edges():
+    bins = [0.0, 1e-3, 0.01, 0.1, 1.0, 5.0, 20.0]
+    e1 = [1e-11, 1e-4, 0.5, 6.0, 20.0]
+    eouts = [[0.05, 0.3, 1.0, 2.5, 7.0, 12.0],        # starts above two edges, an E_out on an edge, ends below the top
+             [0.0, 15.0],                             # NP = 2, ends below the top edge
+             [0.0, 0.01, 0.4, 1.0, 3.0, 20.0],        # two E_out on edges, ends on the top edge
+             [0.02, 0.5, 2.0, 8.0, 25.0],             # starts above two edges, ends above the top edge
+             [0.0, 1.0, 30.0]]
+    rxns = [(19, 1, 2.0, [(4, law4_rows(e1, eouts, [0.5, 1.0, 1.5, 2.5, 4.0]))]),
+            (20, 20, 0.6, [(4, _law4([1e-11, 3e-3, 2.0, 20.0], 431, e_max=10.0, scheme=1))])]
+    delayed = [(4, law4_rows([1e-11, 20.0], [[0.0, 4.0], [0.0, 5.0]], [0.4, 0.5]))]
+    return _chi_assemble(_geom(1e-10, 1.94, 40, last=20.0), rxns, delayed, _lin_yields(1), bins, arith=True,
+                         why="law-4 rows whose first E_out lies above the lowest two group edges, rows that end "
+                             "below the top edge, a row with NP = 2, group edges equal to E_out points; a union "
+                             "energy below the first nuclide energy")
+
+
+def _groups_nuclide(bins, G):
+    rxns = [(19, 1, 2.0, [(4, _law4([1e-11, 1e-3, 1.0, 20.0], 441)),
+                          (7, _arr(tab1_block([1e-11, 2e-5, 0.3, 20.0], [1.3, 1.32, 1.4, 1.45]), [-20.0]))])]
+    delayed = [(4, _law4([1e-11, 0.7, 20.0], 442, n_pts=7, e_max=3.0))]
+    return _chi_assemble(NUC_E, rxns, delayed, _lin_yields(1), bins,
+                         why=f"G = {G}: one prompt chain (law 4, then law 7) and one precursor group")
+
+
+def _case_many_energies():
+    e4 = _geom(1e-11, 2.06, 40, last=20.0)
+    T7 = tab1_block(_geom(1.6e-11, 2.3, 34), np.linspace(1.2, 1.5, 34))          # staggered against e4
+    T9 = tab1_block(_geom(2.5e-11, 2.4, 32), np.linspace(1.0, 2.0, 32))
+    Td = tab1_block(_geom(4e-11, 2.5, 30), np.linspace(0.4, 0.5, 30))
+    rxns = [(19, 1, 2.0, [(4, _law4(e4, 451, n_pts=6, e_max=12.0, dw=0.1))]), (20, 10, 0.6, [(7, _arr(T7, [-20.0]))]),
+            (21, 25, 0.3, [(9, _arr(T9, [-5.0]))])]
+    return _chi_assemble(NUC_E, rxns, [(7, _arr(Td, [-20.0]))], _lin_yields(1), [0.0, 1.0, 20.0],
+                         why="a union grid of at least 130 incoming energies (more than two blocks of 64 threads, the "
+                             "last one partial), G = 2")
+
+
+def _dup_grid(n, k):
+    e = _geom(1e-11, 2.65, n, last=20.0)
+    e[k + 1] = e[k]
+    return e
+
+
+def _case_dup_energy():
+    e = _dup_grid(30, 14)
+    a = float(e[14])
+    rxns = [(19, 1, 2.0, [(4, _law4([1e-11, _ulps(a, -1), a, _ulps(a, 1), 20.0], 461))]),
+            (20, 12, 0.6, [(4, _law4([1e-11, 0.5 * a, 2.0 * a, 20.0], 462, scheme=1))])]
+    delayed = [(4, _law4([1e-11, 20.0], 463, n_pts=7, e_max=3.0))]
+    return _chi_assemble(e, rxns, delayed, _lin_yields(1), CHI_BINS7, arith=True,
+                         why="a nuclide grid with one interior duplicated pair; spectrum energies one ulp below the "
+                             "pair, at it and one ulp above it")
+
+
+def _case_dup_leading():
+    e = _geom(1e-9, 2.25, 30, last=20.0)
+    e[1] = e[0]
+    rxns = [(19, 1, 2.0, [(4, _law4([1e-11, float(e[0]), 1e-3, 20.0], 466))]),
+            (20, 2, 0.6, [(4, _law4([1e-10, 0.2, 20.0], 467, scheme=1))])]
+    delayed = [(4, _law4([1e-11, 20.0], 468, n_pts=7, e_max=3.0))]
+    return _chi_assemble(e, rxns, delayed, _lin_yields(1), CHI_BINS7, arith=True,
+                         why="the first two nuclide energies are equal and union energies lie below them: the only "
+                             "way an in-range input reaches `energy(j) == energy(j+1)`; a reaction with threshold 2 "
+                             "is then above its threshold")
+
+
+def _case_overflow():
+    Td = tab1_regions([1e-11, 1.0, 20.0], [0.02, 0.5, 0.5], [3], [1])      # histogram: T = 0.02 below 1 MeV
+    rxns = [(19, 1, 2.0, [(4, _law4([1e-11, 1e-4, 2.0, 5.0, 12.0, 20.0], 471))])]
+    delayed = [(7, _arr(Td, [-20.0])), (7, _arr(tab1_block([1e-11, 20.0], [0.4, 0.45]), [-20.0]))]
+    return _chi_assemble(NUC_E, rxns, delayed, _lin_yields(2), [0.0, 1e-3, 0.03, 0.15, 0.75, 4.0, 20.0],
+                         why="a delayed Maxwell spectrum with T = 0.02 below 1 MeV: exp(Egp1 / T) overflows for the top "
+                             "edge only (20 / 0.02 = 1000, next edge 200; 709.78 decides), inf * 0 = NaN in that row")
+
+
+def _case_no_delayed():
+    rxns = [(19, 1, 2.0, [(4, _law4([1e-11, 1e-3, 1.0, 20.0], 481)),
+                          (7, _arr(tab1_block([1e-11, 2e-5, 0.3, 20.0], [1.3, 1.32, 1.4, 1.45]), [-20.0]))]),
+            (20, 20, 0.6, [(9, _arr(tab1_block([1e-11, 2.0, 4.0, 9.0, 20.0], [0.8, 0.9, 1.0, 1.1, 1.3]), [2.0]))])]
+    return _chi_assemble(NUC_E, rxns, [], [], CHI_BINS7, why="nu_d_type = 0 and no precursor group")
+
+
+def _case_p_valid():
+    pv3 = dict(pv_x=[1e-11, 1e-7, 1e-4, 1e-2, 0.5, 4.0, 20.0], pv_y=[0.9, 0.8, 0.85, 0.6, 0.5, 0.3, 0.25],
+               pv_nbt=[3, 5, 7], pv_int=[2, 4, 3])
+    pv_no_regions = dict(pv_x=[1e-11, 1.0, 20.0], pv_y=[0.3, 0.6, 0.2])                 # ignored (sic), :210
+    pv_last = dict(pv_x=[1e-11, 5.0, 20.0], pv_y=[0.7, 0.4, 0.1], pv_nbt=[3], pv_int=[2])   # ignored: no next
+    rxns = [(19, 1, 2.0, [(4, _law4([1e-11, 1e-3, 1.0, 9.0, 20.0], 491), pv3),
+                          (7, _arr(tab1_block([1e-11, 3e-9, 2e-5, 0.1, 20.0], [1.3, 1.31, 1.32, 1.4, 1.45]), [-20.0]),
+                           pv_no_regions),
+                          (9, _arr(tab1_block([1e-11, 2.0, 20.0], [1.0, 1.2, 1.5]), [-5.0]), pv_last)]),
+            (20, 25, 0.6, [(4, _law4([1e-11, 5e-6, 0.03, 20.0], 492, scheme=1))])]
+    delayed = [(4, _law4([1e-11, 20.0], 493, n_pts=7, e_max=3.0))]
+    return _chi_assemble(NUC_E, rxns, delayed, _lin_yields(1), CHI_BINS7,
+                         why="a nested chain whose first spectrum has a three-region p_valid with union energies "
+                             "strictly inside every region, a second with pairs but n_regions = 0 and a p_valid on "
+                             "the last spectrum (both ignored)")
+
+
+def chi_edge_cases():
+    """Ordered name -> case, each in the layout of chi_case() (entries of spectra may be
+    (law, data, p_valid dict)) with its own `bins`, the condition it exists for (`why`; computed
+    from the inputs by tests/test_chi_edges.py) and `arith`.  groups_1_and_70 is one nuclide under
+    two group structures, hence two entries."""
+    bins70 = np.concatenate([[0.0], _geom(1e-11, 1.5076, 70, last=20.0)])       # log-spaced, as test_sab's 70 groups
+    return {"arith_only": _case_arith_only(), "tab1_schemes": _case_tab1_schemes(), "thresholds": _case_thresholds(),
+            "nearest_row": _case_nearest_row(), "eout_edges": _case_eout_edges(),
+            "groups_1": _groups_nuclide([0.0, 20.0], 1), "groups_70": _groups_nuclide(bins70, 70),
+            "many_energies": _case_many_energies(), "dup_energy": _case_dup_energy(),
+            "dup_leading": _case_dup_leading(), "overflow": _case_overflow(), "no_delayed": _case_no_delayed(),
+            "p_valid": _case_p_valid()}
+
+
 # ---- raw ACE blocks for the ACE -> tabular conversion (convert_file4 / convert_file6) ----
 def _ang_table(rng, interp, npts, positive=False):
     """[JJ, NP, cosines(NP), pdf(NP), cdf(NP)] of one ACE tabular angular distribution."""
