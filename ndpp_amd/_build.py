@@ -28,7 +28,7 @@ SOURCES = [(CSRC / "ndpp_hip.hip", False), (CSRC / "fg_strict_stages.hip", True)
            (CSRC / "thin_kernels.hip", True), (CSRC / "compare_kernels.hip", True),
            (CSRC / "minimum_kernels.hip", True)]
 HEADERS = [CSRC / "ndpp_math.h", CSRC / "fg_pipeline.h", CSRC / "fg_device.h", CSRC / "kernels.h", CSRC / "dev_util.h",
-           CSRC / "file6_device.h",
+           CSRC / "file6_device.h", CSRC / "section_util.h",
            CSRC / "legendre_int.h", CSRC / "legendre_ref_forms.h", CSRC / "exp_tab.inc",
            PKG.parent / "include" / "ndpp_hip.h"]
 

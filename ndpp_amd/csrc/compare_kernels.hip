@@ -1,12 +1,12 @@
 // compare_kernels.hip -- how far two libraries are apart (include/ndpp_hip.h):
 // the rows a consumer interpolates from section A and from section B at the same energy, under the
-// scale-relative metric of ndpp_grid_error.  Nothing in the reference does this.  Both sections are
-// read linearly in ln E (the rule of thin.hip):
+// scale-relative metric of section_util.h.  Nothing in the reference does this.  Both sections are
+// read linearly in ln E (lne_weight, section_util.h):
 //   A(x)   = ya[i] + (ya[i1] - ya[i]) fa      i the largest index with xa[i] <= x, i1 = min(i+1, na-1)
 //   B(x)   = yb[j] + (yb[j1] - yb[j]) fb
 //   d(g,l) = | A(x) - B(x) |                  g < G, l < Lc = min(La, Lb)
-//   err    = max d / max_g |P0| over the four rows            (0 when that scale is 0)
-//   worst[g][l] = max over the queries of d(g,l) / scale
+//   err    = the metric over d, the scale from the four rows
+//   worst[g][l] = max over the queries of rel_err(d(g,l), scale)
 //
 // i, fa, j, fb are computed on the host, once per query, and uploaded: the kernels are + - * / fabs
 // and comparisons only, built without contraction, so a host restatement with the same operation
@@ -14,10 +14,9 @@
 //
 // compare_error_kernel: one wave64 per query, the grid strides over queries.  The four rows are
 // G*La or G*Lb contiguous doubles each; the lanes stride over the G*Lc compared elements (with
-// La == Lb these are the whole rows, coalesced; otherwise runs of Lc doubles at pitch La or Lb),
-// each lane keeps its running (value, index) maximum in ascending index order, one butterfly over
-// the wave folds them with "larger value, then lower index", and lane 0 writes err, arg and the
-// scale.  No LDS, no atomics.  Memory-bound: (2 La + 2 Lb) * G * 8 bytes per query.
+// La == Lb these are the whole rows, coalesced; otherwise runs of Lc doubles at pitch La or Lb)
+// and fold their maxima as WaveMax (section_util.h) says; lane 0 writes err, arg and the scale.
+// No LDS, no atomics.  Memory-bound: (2 La + 2 Lb) * G * 8 bytes per query.
 //
 // worst needs a maximum across queries per element.  The first kernel cannot keep it: a lane owns
 // ceil(G*Lc / 64) elements, a number without a bound, and d / scale needs the scale the wave only
@@ -38,6 +37,7 @@
 #include "../../include/ndpp_hip.h"
 #include "dev_util.h"
 #include "kernels.h"
+#include "section_util.h"
 
 namespace ndpp {
 namespace {
@@ -69,31 +69,21 @@ compare_error_kernel(int nq, int G, int La, int Lb, int Lc, int na, int nb, cons
     const double* a1 = ya + (size_t)min(i + 1, na - 1) * pa;
     const double* b0 = yb + (size_t)j * pb;
     const double* b1 = yb + (size_t)min(j + 1, nb - 1) * pb;
-    double dmax = -1.0, scale = 0.0;
-    int imax = INT_MAX, ibad = INT_MAX;
+    WaveMax w;
     int g = g0, l = l0;
     for (int e = lane; e < GLc; e += 64) {
       const int oa = g * La + l, ob = g * Lb + l;
       const double va0 = a0[oa], va1 = a1[oa], vb0 = b0[ob], vb1 = b1[ob];
-      const double d = fabs((va0 + (va1 - va0) * fqa) - (vb0 + (vb1 - vb0) * fqb));
-      if (!(d < INFINITY)) { if (e < ibad) ibad = e; }    // NaN or infinite
-      else if (d > dmax) { dmax = d; imax = e; }
-      if (l == 0) scale = fmax(scale, fmax(fmax(fabs(va0), fabs(va1)), fmax(fabs(vb0), fabs(vb1))));
+      w.take(e, fabs((va0 + (va1 - va0) * fqa) - (vb0 + (vb1 - vb0) * fqb)));
+      if (l == 0) w.scale = fmax(w.scale, fmax(fmax(fabs(va0), fabs(va1)), fmax(fabs(vb0), fabs(vb1))));
       g += dg;
       l += dl;
       if (l >= Lc) { l -= Lc; ++g; }
     }
-    for (int o = 32; o > 0; o >>= 1) {
-      const double v = __shfl_xor(dmax, o);
-      const int k = __shfl_xor(imax, o);
-      if (v > dmax || (v == dmax && k < imax)) { dmax = v; imax = k; }
-      ibad = min(ibad, __shfl_xor(ibad, o));
-      scale = fmax(scale, __shfl_xor(scale, o));
-    }
+    w.fold();
     if (lane == 0) {
-      if (ibad != INT_MAX) { err[q] = INFINITY; arg[q] = ibad; }
-      else { err[q] = scale == 0.0 ? 0.0 : dmax / scale; arg[q] = imax; }
-      scale_out[q] = scale;
+      w.write(&err[q], &arg[q]);
+      scale_out[q] = w.scale;
     }
   }
 }
@@ -122,8 +112,7 @@ compare_worst_kernel(int nq, int per, int G, int La, int Lb, int Lc, int na, int
     const double va0 = pya[(size_t)i * pa], va1 = pya[(size_t)min(i + 1, na - 1) * pa];
     const double vb0 = pyb[(size_t)j * pb], vb1 = pyb[(size_t)min(j + 1, nb - 1) * pb];
     const double d = fabs((va0 + (va1 - va0) * fa[q]) - (vb0 + (vb1 - vb0) * fb[q]));
-    const double s = scale[q];
-    const double v = !(d < INFINITY) ? INFINITY : (s == 0.0 ? 0.0 : d / s);
+    const double v = rel_err(d, scale[q]);
     w = v > w ? v : w;
   }
   part[(size_t)c * GLc + e] = w;
@@ -141,19 +130,11 @@ compare_fold_kernel(int GLc, int n_chunks, const double* __restrict__ part, doub
   worst[e] = w;
 }
 
-int check_grid(const char* name, int n, const double* x) {
-  for (int i = 0; i < n; ++i)
-    if (!(std::isfinite(x[i]) && x[i] > 0.0 && (i == 0 || x[i] > x[i - 1])))
-      return fail(NDPP_EINVAL, "lib_compare: %s[%d] = %.17g: %s must be strictly increasing, positive and finite",
-                  name, i, x[i], name);
-  return NDPP_OK;
-}
-
 // the largest i with x[i] <= v and the weight of row i + 1; v inside [x[0], x[n-1]]
 void bracket(int n, const double* x, double v, int* i_out, double* f_out) {
   const int i = (int)(std::upper_bound(x, x + n, v) - x) - 1;
   *i_out = i;
-  *f_out = (v == x[i] || i == n - 1) ? 0.0 : std::log(v / x[i]) / std::log(x[i + 1] / x[i]);
+  *f_out = (v == x[i] || i == n - 1) ? 0.0 : lne_weight(x[i], x[i + 1], v);
 }
 
 }  // namespace
@@ -171,12 +152,10 @@ extern "C" int ndpp_lib_compare(int G, int La, int Lb, int na, const double* xa,
   if (!xa || !ya || !xb || !yb || !xq || !err || !arg)
     return fail(NDPP_EINVAL, "lib_compare: NULL argument (only worst may be NULL)");
   const int Lmax = std::max(La, Lb), Lc = std::min(La, Lb);
-  if ((long)G * Lmax > INT_MAX / 2)
-    return fail(NDPP_EINVAL, "lib_compare: G * L = %ld does not fit an index", (long)G * Lmax);
-  int rc = check_grid("xa", na, xa);
+  int rc = check_gl_index("lib_compare", G, Lmax);
   if (rc != NDPP_OK) return rc;
-  rc = check_grid("xb", nb, xb);
-  if (rc != NDPP_OK) return rc;
+  if ((rc = check_energy_grid("lib_compare", "xa", na, xa))) return rc;
+  if ((rc = check_energy_grid("lib_compare", "xb", nb, xb))) return rc;
   if ((rc = require_device("lib_compare"))) return rc;
 
   // rows and weights per query; row -1 marks the queries that are skipped: not positive and finite, or
@@ -229,9 +208,7 @@ extern "C" int ndpp_lib_compare(int G, int La, int Lb, int na, const double* xa,
       hipLaunchKernelGGL(compare_fold_kernel, dim3(nblk(GLc, kThreads)), dim3(kThreads), 0, 0, GLc, chunks, d_part.p,
                          d_worst.p);
     }
-    span.end();
-    NDPP_TRY(hipGetLastError());
-    NDPP_TRY(hipDeviceSynchronize());
+    NDPP_CLOSE_SPAN(span);
   }
   NDPP_TRY(d_err.download(err, nq));
   NDPP_TRY(d_arg.download(arg, nq));

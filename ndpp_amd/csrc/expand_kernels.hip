@@ -5,7 +5,7 @@
 // and :345-396 (test_scatt_positivity); the rules (band, zero rows, NaN) are in ndpp_hip.h.
 //
 // Both kernels take the basis B[j][l] = (l + 1/2) P_l(mu_j), computed once per call on the
-// host from the closed forms pn<l> (ndpp_math.h, the reference's calc_pn), and evaluate
+// host from the closed forms pn_rt (ndpp_math.h, the reference's calc_pn), and evaluate
 //   f = B[j][0] a_0;  f = fma(B[j][l], a_l, f)  for l = 1 .. n_mom-1
 // -- one fixed operation sequence, so expand and positivity agree bit for bit and every
 // call repeats its bits.
@@ -13,8 +13,8 @@
 // Positivity: one thread per (E_in, group) row, its n_mom moments in VGPRs; the lanes of a
 // wave walk the mu grid in lockstep, so B[j][*] is wave-uniform and is read by scalar loads
 // into SGPRs (the operand v_fma_f64 takes for free).  Per (row, mu): n_mom FMAs, one min, one
-// add (the NaN witness).  A block holds whole incoming energies, so the band (first / last
-// group with P0 > 0) is found in LDS from the P0 values the block reads anyway.  Offending rows
+// add (the NaN witness).  A block holds whole incoming energies (block_shape, section_util.h), so
+// the band is found in LDS from the P0 values the block reads anyway (block_band).  Offending rows
 // are compacted in (iE, g) order per block (ballot + wave offsets), then a one-block kernel
 // scans the per-block counts and folds the summary, and a gather copies the first `cap`
 // offenders to the output.  Nothing of size rows x M touches memory.
@@ -26,11 +26,11 @@
 #include "dev_util.h"
 #include "kernels.h"
 #include "ndpp_math.h"
+#include "section_util.h"
 
 namespace ndpp {
 namespace {
 
-constexpr int kMaxBlock = 512;        // positivity block: at most 8 waves
 constexpr int kFinalThreads = 1024;
 
 struct PosPart {                      // per-block partial of the summary
@@ -73,14 +73,7 @@ positivity_kernel(int n_ein, int G, int L, int epb, const double* __restrict__ m
   const int R = ne * G;
   const long slot0 = (long)blockIdx.x * epb * G;     // this block's region of the candidate arrays
 
-  // the band of every incoming energy of the block: first / last group with P0 > 0
-  for (int e = tid; e < ne; e += B) { s_gmin[e] = G; s_gmax[e] = -1; }
-  __syncthreads();
-  for (int r = tid; r < R; r += B) {
-    const int e = r / G, g = r - e * G;
-    if (mat[(size_t)(e0 * G + r) * L] > 0.0) { atomicMin(&s_gmin[e], g); atomicMax(&s_gmax[e], g); }
-  }
-  __syncthreads();
+  block_band(mat, e0, ne, G, L, s_gmin, s_gmax);
 
   long rows = 0, kmin = LONG_MAX;
   double vmin = INFINITY;
@@ -232,27 +225,12 @@ __global__ void expand_kernel(long total, int n_mu, int L, const double* __restr
   }
 }
 
-double closed_pn(int l, double x) {
-  switch (l) {
-    case 0: return pn<0>(x);
-    case 1: return pn<1>(x);
-    case 2: return pn<2>(x);
-    case 3: return pn<3>(x);
-    case 4: return pn<4>(x);
-    case 5: return pn<5>(x);
-    case 6: return pn<6>(x);
-    case 7: return pn<7>(x);
-    case 8: return pn<8>(x);
-    case 9: return pn<9>(x);
-    default: return pn<10>(x);
-  }
-}
-
-// B[j][l] = (l + 1/2) P_l(mu_j), the basis of both kernels
+// B[j][l] = (l + 1/2) P_l(mu_j), the basis of both kernels (nm <= NDPP_MAX_ORDER = 11, so l <= 10 and
+// pn_rt's default branch is not reached)
 std::vector<double> make_basis(int n_mu, const double* mu, int nm) {
   std::vector<double> b((size_t)n_mu * nm);
   for (int j = 0; j < n_mu; ++j)
-    for (int l = 0; l < nm; ++l) b[(size_t)j * nm + l] = ((double)l + 0.5) * closed_pn(l, mu[j]);
+    for (int l = 0; l < nm; ++l) b[(size_t)j * nm + l] = ((double)l + 0.5) * pn_rt(l, mu[j]);
   return b;
 }
 
@@ -272,55 +250,6 @@ int check_mu(const char* who, int n_mu, const double* mu) {
       return fail(NDPP_EINVAL, "%s: mu[%d]=%g is not a finite value in [-1, 1]", who, j, mu[j]);
   return NDPP_OK;
 }
-
-// a * b * c bytes without overflow (and below 2^62, so that every signed index fits)
-bool bytes_of(size_t a, size_t b, size_t c, size_t* out) {
-  size_t ab;
-  return !__builtin_mul_overflow(a, b, &ab) && !__builtin_mul_overflow(ab, c, out) && *out < ((size_t)1 << 62);
-}
-
-// incoming energies per positivity block and the block size: whole energies per block, as few
-// idle lanes as possible (G = 7: 64 energies on 448 threads; G = 70: 7 on 512 -> 490 rows)
-void positivity_shape(int G, int* epb, int* threads) {
-  int best_e = 1, best_b = kMaxBlock;
-  double best_waste = 2.0;
-  const int emax = std::max(1, kMaxBlock / G);
-  for (int e = 1; e <= emax; ++e) {
-    const long R = (long)e * G;
-    const long passes = (R + kMaxBlock - 1) / kMaxBlock;
-    const long b = ((R + passes - 1) / passes + 63) / 64 * 64;
-    const double waste = (double)(passes * b - R) / (double)(passes * b);
-    if (waste <= best_waste) { best_waste = waste; best_e = e; best_b = (int)b; }
-  }
-  *epb = best_e;
-  *threads = best_b;
-}
-
-template <int NM>
-void launch_positivity(int nblk, int threads, int n_ein, int G, int L, int epb, const double* mat, int n_mu,
-                       const double* basis, PosPart* part, int* cand_row, double* cand_min, int* cand_mu) {
-  hipLaunchKernelGGL(positivity_kernel<NM>, dim3(nblk), dim3(threads), 0, 0, n_ein, G, L, epb, mat, n_mu, basis,
-                     part, cand_row, cand_min, cand_mu);
-}
-
-template <int NM>
-void launch_expand(long total, int n_mu, int L, const double* mom, const double* basis, double* out) {
-  const int threads = 256;
-  hipLaunchKernelGGL(expand_kernel<NM>, dim3(nblk(total, threads)), dim3(threads), 0, 0, total, n_mu, L, mom,
-                     basis, out);
-}
-
-using PosLaunch = void (*)(int, int, int, int, int, int, const double*, int, const double*, PosPart*, int*,
-                           double*, int*);
-constexpr PosLaunch kPosLaunch[NDPP_MAX_ORDER] = {
-    launch_positivity<1>, launch_positivity<2>, launch_positivity<3>, launch_positivity<4>,
-    launch_positivity<5>, launch_positivity<6>, launch_positivity<7>, launch_positivity<8>,
-    launch_positivity<9>, launch_positivity<10>, launch_positivity<11>};
-using ExpLaunch = void (*)(long, int, int, const double*, const double*, double*);
-constexpr ExpLaunch kExpLaunch[NDPP_MAX_ORDER] = {
-    launch_expand<1>, launch_expand<2>, launch_expand<3>, launch_expand<4>, launch_expand<5>,
-    launch_expand<6>, launch_expand<7>, launch_expand<8>, launch_expand<9>, launch_expand<10>,
-    launch_expand<11>};
 
 }  // namespace
 }  // namespace ndpp
@@ -348,7 +277,7 @@ extern "C" int ndpp_scatt_positivity(int n_ein, int G, int L, const double* mat,
 
   const std::vector<double> basis = make_basis(n_mu, mu, n_moments);
   int epb = 1, threads = 64;
-  positivity_shape(G, &epb, &threads);
+  block_shape(G, &epb, &threads);
   const int nblk = (n_ein + epb - 1) / epb;
   const long slot_stride = (long)epb * G;
   const long slots = (long)nblk * slot_stride;
@@ -371,15 +300,15 @@ extern "C" int ndpp_scatt_positivity(int n_ein, int G, int L, const double* mat,
   NDPP_TRY(d_omu.alloc(n_out_max));
   {
     GpuSpan span(nullptr, -1);
-    kPosLaunch[n_moments - 1](nblk, threads, n_ein, G, L, epb, d_mat.p, n_mu, d_basis.p, d_part.p, d_crow.p,
-                              d_cmin.p, d_cmu.p);
+    dispatch_moments(n_moments, [&](auto nm) {
+      hipLaunchKernelGGL(positivity_kernel<decltype(nm)::value>, dim3(nblk), dim3(threads), 0, 0, n_ein, G, L, epb, d_mat.p, n_mu,
+                         d_basis.p, d_part.p, d_crow.p, d_cmin.p, d_cmu.p);
+    });
     hipLaunchKernelGGL(positivity_final, dim3(1), dim3(kFinalThreads), 0, 0, nblk, d_part.p, d_boff.p, d_sum.p);
     if (n_out_max > 0)
       hipLaunchKernelGGL(positivity_gather, dim3(nblk), dim3(256), 0, 0, slot_stride, n_out_max, d_part.p,
                          d_boff.p, d_crow.p, d_cmin.p, d_cmu.p, d_orow.p, d_omin.p, d_omu.p);
-    span.end();
-    NDPP_TRY(hipGetLastError());
-    NDPP_TRY(hipDeviceSynchronize());
+    NDPP_CLOSE_SPAN(span);
   }
   PosSum s;
   NDPP_TRY(hipMemcpy(&s, d_sum.p, sizeof(s), hipMemcpyDeviceToHost));
@@ -421,10 +350,11 @@ extern "C" int ndpp_expand_moments(int n_ein, int L, const double* moments, int 
   NDPP_TRY(d_out.alloc(total));
   {
     GpuSpan span(nullptr, -1);
-    kExpLaunch[n_moments - 1](total, n_mu, L, d_mom.p, d_basis.p, d_out.p);
-    span.end();
-    NDPP_TRY(hipGetLastError());
-    NDPP_TRY(hipDeviceSynchronize());
+    dispatch_moments(n_moments, [&](auto nm) {
+      hipLaunchKernelGGL(expand_kernel<decltype(nm)::value>, dim3(nblk(total, 256)), dim3(256), 0, 0, total, n_mu, L, d_mom.p,
+                         d_basis.p, d_out.p);
+    });
+    NDPP_CLOSE_SPAN(span);
   }
   NDPP_TRY(hipMemcpy(out, d_out.p, sizeof(double) * total, hipMemcpyDeviceToHost));
   return NDPP_OK;

@@ -1,19 +1,18 @@
 // grid_kernels.hip -- what interpolating between two neighbours of an incoming-energy grid costs:
 // the error of the interpolated row against a freshly integrated row at a point between them.
 // Nothing in the reference does this (thin_grid, thin.F90, compares stored rows with each other);
-// the interpolation rule is the one thin_grid assumes, linear in ln E (thin.hip):
+// the interpolation rule is the one thin_grid assumes, linear in ln E (lne_weight, section_util.h):
 //   f      = ln(x_mid / x_i) / ln(x_{i+1} / x_i)
 //   d(g,l) = | y_i + (y_{i+1} - y_i) f - y_mid |
-//   err_i  = max d / max_g |P0| over the three rows          (0 when that scale is 0)
+//   err_i  = the scale-relative metric of section_util.h over d, the scale from the three rows
 //
 // f is computed on the host, once per interval, and uploaded: the kernel is + - * / fabs and
 // comparisons only, built without contraction, so a host restatement with the same operation
 // order gives the same bits (ndpp_amd/gridcheck.py: grid_error_numpy).
 //
 // One wave64 per interval, the grid strides over intervals.  The three rows are G*L contiguous
-// doubles each; the lanes stride over them (coalesced loads), each lane keeps its running
-// (value, index) maximum in ascending index order, one butterfly over the wave folds them with
-// "larger value, then lower index", and lane 0 writes the two results.  No LDS, no atomics.
+// doubles each; the lanes stride over them (coalesced loads) and fold their maxima as WaveMax
+// (section_util.h) says; lane 0 writes the two results.  No LDS, no atomics.
 // Memory-bound: 3 * G * L * 8 bytes per interval.
 #include <climits>
 #include <cmath>
@@ -22,6 +21,7 @@
 #include "../../include/ndpp_hip.h"
 #include "dev_util.h"
 #include "kernels.h"
+#include "section_util.h"
 
 namespace ndpp {
 namespace {
@@ -43,26 +43,14 @@ grid_error_kernel(int n_int, int GL, int L, const double* __restrict__ y, const 
     const double* a = y + (size_t)i * GL;
     const double* b = a + GL;
     const double* m = y_mid + (size_t)i * GL;
-    double dmax = -1.0, scale = 0.0;
-    int imax = INT_MAX, ibad = INT_MAX;
+    WaveMax w;
     for (int e = lane; e < GL; e += 64) {
       const double ya = a[e], yb = b[e], ym = m[e];
-      const double d = fabs(ya + (yb - ya) * fi - ym);
-      if (!(d < INFINITY)) { if (e < ibad) ibad = e; }    // NaN or infinite
-      else if (d > dmax) { dmax = d; imax = e; }
-      if (e % L == 0) scale = fmax(scale, fmax(fabs(ya), fmax(fabs(yb), fabs(ym))));
+      w.take(e, fabs(ya + (yb - ya) * fi - ym));
+      if (e % L == 0) w.scale = fmax(w.scale, fmax(fabs(ya), fmax(fabs(yb), fabs(ym))));
     }
-    for (int o = 32; o > 0; o >>= 1) {
-      const double v = __shfl_xor(dmax, o);
-      const int k = __shfl_xor(imax, o);
-      if (v > dmax || (v == dmax && k < imax)) { dmax = v; imax = k; }
-      ibad = min(ibad, __shfl_xor(ibad, o));
-      scale = fmax(scale, __shfl_xor(scale, o));
-    }
-    if (lane == 0) {
-      if (ibad != INT_MAX) { err[i] = INFINITY; arg[i] = ibad; }
-      else { err[i] = scale == 0.0 ? 0.0 : dmax / scale; arg[i] = imax; }
-    }
+    w.fold();
+    if (lane == 0) w.write(&err[i], &arg[i]);
   }
 }
 
@@ -75,7 +63,7 @@ extern "C" int ndpp_grid_error(int L, int G, int n, const double* x, const doubl
                                const double* y_mid, double* err, int* arg) {
   if (L < 1 || G < 1 || n < 2) return fail(NDPP_EINVAL, "grid_error: L=%d G=%d n=%d (need L, G >= 1, n >= 2)", L, G, n);
   if (!x || !y || !x_mid || !y_mid || !err || !arg) return fail(NDPP_EINVAL, "grid_error: NULL argument");
-  if ((long)G * L > INT_MAX / 2) return fail(NDPP_EINVAL, "grid_error: G * L = %ld does not fit an index", (long)G * L);
+  if (int rc = check_gl_index("grid_error", G, L)) return rc;
   const int GL = G * L, n_int = n - 1;
   if (int rc = require_device()) return rc;
 
@@ -85,7 +73,7 @@ extern "C" int ndpp_grid_error(int L, int G, int n, const double* x, const doubl
   for (int i = 0; i < n_int; ++i) {
     const double x0 = x[i], x1 = x[i + 1], xm = x_mid[i];
     const bool ok = std::isfinite(x0) && std::isfinite(x1) && x0 > 0.0 && x1 > x0 && xm > x0 && xm < x1;
-    f[i] = ok ? std::log(xm / x0) / std::log(x1 / x0) : -1.0;
+    f[i] = ok ? lne_weight(x0, x1, xm) : -1.0;
   }
   DevBuf<double> d_y, d_mid, d_f, d_err;
   DevBuf<int> d_arg;
@@ -98,9 +86,7 @@ extern "C" int ndpp_grid_error(int L, int G, int n, const double* x, const doubl
     GpuSpan span(nullptr, -1);
     hipLaunchKernelGGL(grid_error_kernel, dim3(nblk((long)n_int * 64, kThreads)), dim3(kThreads), 0, 0, n_int, GL, L,
                        d_y.p, d_mid.p, d_f.p, d_err.p, d_arg.p);
-    span.end();
-    NDPP_TRY(hipGetLastError());
-    NDPP_TRY(hipDeviceSynchronize());
+    NDPP_CLOSE_SPAN(span);
   }
   NDPP_TRY(hipMemcpy(err, d_err.p, sizeof(double) * n_int, hipMemcpyDeviceToHost));
   NDPP_TRY(hipMemcpy(arg, d_arg.p, sizeof(int) * n_int, hipMemcpyDeviceToHost));

@@ -43,6 +43,25 @@ auto dispatch_lmax(int L, F&& f) {
   if (L <= 8) return f(std::integral_constant<int, 8>());
   return f(std::integral_constant<int, 11>());
 }
+// f(std::integral_constant<int, N>) with N = n_moments, 1 <= n_moments <= NDPP_MAX_ORDER (checked by
+// the caller): the library analyses are instantiated for every number of moments they evaluate
+template <class F>
+void dispatch_moments(int n_moments, F&& f) {
+  static_assert(NDPP_MAX_ORDER == 11, "one case per number of moments");
+  switch (n_moments) {
+    case 1: return f(std::integral_constant<int, 1>());
+    case 2: return f(std::integral_constant<int, 2>());
+    case 3: return f(std::integral_constant<int, 3>());
+    case 4: return f(std::integral_constant<int, 4>());
+    case 5: return f(std::integral_constant<int, 5>());
+    case 6: return f(std::integral_constant<int, 6>());
+    case 7: return f(std::integral_constant<int, 7>());
+    case 8: return f(std::integral_constant<int, 8>());
+    case 9: return f(std::integral_constant<int, 9>());
+    case 10: return f(std::integral_constant<int, 10>());
+    default: return f(std::integral_constant<int, 11>());
+  }
+}
 
 // hipEvent bracket around the kernels of one batch call: the span between
 // construction and end() is what ndpp_last_gpu_ms() reports (uploads, downloads

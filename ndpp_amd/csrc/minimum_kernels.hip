@@ -9,7 +9,7 @@
 // M2 = sum_{l >= 2} |c_l| (l-1) l (l+1) (l+2) / 8 >= max |f''|.
 //
 // One thread per row, its c_l in VGPRs; a block holds whole incoming energies, so the band comes from
-// LDS as in positivity_kernel.  Per row:
+// LDS (block_shape and block_band, section_util.h).  Per row:
 //   1. f at the 65 nodes of 64 equal panels.  The nodes are the same for every lane, so the host-built
 //      P_l(node) is read by scalar loads.  hi = the smallest node value.
 //   2. the nodes once more (keeping 65 values would cost 130 VGPRs): a panel whose bound is within
@@ -33,11 +33,11 @@
 #include "../../include/ndpp_hip.h"
 #include "dev_util.h"
 #include "kernels.h"
+#include "section_util.h"
 
 namespace ndpp {
 namespace {
 
-constexpr int kMaxBlock = 512;             // at most 8 waves, as positivity_kernel
 constexpr int kPanels = 64;                // first pass: 64 equal panels, 65 nodes
 constexpr double kPanelWidth = 2.0 / kPanels;
 constexpr int kMaxDepth = 45;              // levels below the panels: h >= 2^-50, ends stay exact
@@ -217,14 +217,7 @@ minimum_kernel(int n_ein, int G, int L, int epb, const double* __restrict__ mat,
   const int ne = (int)min((long)epb, (long)n_ein - e0);
   const int R = ne * G;
 
-  // the band of every incoming energy of the block: first / last group with P0 > 0
-  for (int e = tid; e < ne; e += B) { s_gmin[e] = G; s_gmax[e] = -1; }
-  __syncthreads();
-  for (int r = tid; r < R; r += B) {
-    const int e = r / G, g = r - e * G;
-    if (mat[(size_t)(e0 * G + r) * L] > 0.0) { atomicMin(&s_gmin[e], g); atomicMax(&s_gmax[e], g); }
-  }
-  __syncthreads();
+  block_band(mat, e0, ne, G, L, s_gmin, s_gmax);
 
   for (int r = tid; r < R; r += B) {
     const int e = r / G, g = r - e * G;
@@ -245,37 +238,6 @@ minimum_kernel(int n_ein, int G, int L, int epb, const double* __restrict__ mat,
   }
 }
 
-// incoming energies per block and the block size: whole energies per block, as few idle lanes as
-// possible (the rule of positivity_shape, expand_kernels.hip)
-void minimum_shape(int G, int* epb, int* threads) {
-  int best_e = 1, best_b = kMaxBlock;
-  double best_waste = 2.0;
-  const int emax = std::max(1, kMaxBlock / G);
-  for (int e = 1; e <= emax; ++e) {
-    const long R = (long)e * G;
-    const long passes = (R + kMaxBlock - 1) / kMaxBlock;
-    const long b = ((R + passes - 1) / passes + 63) / 64 * 64;
-    const double waste = (double)(passes * b - R) / (double)(passes * b);
-    if (waste <= best_waste) { best_waste = waste; best_e = e; best_b = (int)b; }
-  }
-  *epb = best_e;
-  *threads = best_b;
-}
-
-template <int NM>
-void launch_minimum(int nblk, int threads, int n_ein, int G, int L, int epb, const double* mat, double rel_tol,
-                    const double* basis, double* lo, double* hi, double* mu, int* cls, int* evals) {
-  hipLaunchKernelGGL(minimum_kernel<NM>, dim3(nblk), dim3(threads), 0, 0, n_ein, G, L, epb, mat, rel_tol, basis,
-                     lo, hi, mu, cls, evals);
-}
-
-using MinLaunch = void (*)(int, int, int, int, int, int, const double*, double, const double*, double*, double*,
-                           double*, int*, int*);
-constexpr MinLaunch kMinLaunch[NDPP_MAX_ORDER] = {
-    launch_minimum<1>, launch_minimum<2>, launch_minimum<3>, launch_minimum<4>, launch_minimum<5>,
-    launch_minimum<6>, launch_minimum<7>, launch_minimum<8>, launch_minimum<9>, launch_minimum<10>,
-    launch_minimum<11>};
-
 // P_l(node j), l < nm, by eval_f's recurrence
 std::vector<double> node_basis(int nm) {
   std::vector<double> b((size_t)(kPanels + 1) * nm);
@@ -288,12 +250,6 @@ std::vector<double> node_basis(int nm) {
       p[l + 1] = ((double)(2 * l + 1) * x * p[l] - (double)l * p[l - 1]) / (double)(l + 1);
   }
   return b;
-}
-
-// a * b * c bytes without overflow (and below 2^62, so that every signed index fits)
-bool bytes_of(size_t a, size_t b, size_t c, size_t* out) {
-  size_t ab;
-  return !__builtin_mul_overflow(a, b, &ab) && !__builtin_mul_overflow(ab, c, out) && *out < ((size_t)1 << 62);
 }
 
 int minimum_impl(int n_ein, int G, int L, const double* mat, int n_moments, double rel_tol, double* lo,
@@ -318,7 +274,7 @@ int minimum_impl(int n_ein, int G, int L, const double* mat, int n_moments, doub
 
   const std::vector<double> basis = node_basis(n_moments);
   int epb = 1, threads = 64;
-  minimum_shape(G, &epb, &threads);
+  block_shape(G, &epb, &threads);
   const int nblk = (n_ein + epb - 1) / epb;
   const size_t rows = (size_t)n_ein * G;
   DevBuf<double> d_mat, d_basis, d_lo, d_hi, d_mu;
@@ -332,11 +288,11 @@ int minimum_impl(int n_ein, int G, int L, const double* mat, int n_moments, doub
   if (evals) NDPP_TRY(d_evals.alloc(rows));
   {
     GpuSpan span(nullptr, -1);
-    kMinLaunch[n_moments - 1](nblk, threads, n_ein, G, L, epb, d_mat.p, rel_tol, d_basis.p, d_lo.p, d_hi.p,
-                              d_mu.p, d_cls.p, evals ? d_evals.p : nullptr);
-    span.end();
-    NDPP_TRY(hipGetLastError());
-    NDPP_TRY(hipDeviceSynchronize());
+    dispatch_moments(n_moments, [&](auto nm) {
+      hipLaunchKernelGGL(minimum_kernel<decltype(nm)::value>, dim3(nblk), dim3(threads), 0, 0, n_ein, G, L, epb, d_mat.p, rel_tol,
+                         d_basis.p, d_lo.p, d_hi.p, d_mu.p, d_cls.p, evals ? d_evals.p : nullptr);
+    });
+    NDPP_CLOSE_SPAN(span);
   }
   NDPP_TRY(d_lo.download(lo, rows));
   NDPP_TRY(d_hi.download(hi, rows));

@@ -1,10 +1,10 @@
 // thin_kernels.hip -- error-bounded thinning of an incoming-energy grid (include/ndpp_hip.h,
 // DESIGN.md section 13).  For every anchor a and every partner b = a + d within the window, the
 // error of every point k strictly between them against the interpolation between rows a and b,
-// linear in ln E, under the scale-relative metric of ndpp_grid_error:
+// linear in ln E, under the scale-relative metric of section_util.h:
 //   f          = (lx[k] - lx[a]) / (lx[b] - lx[a])
 //   d(a,k,b)   = max_e | y[a][e] + (y[b][e] - y[a][e]) f - y[k][e] |
-//   err(a,k,b) = d / max(s[a], s[k], s[b])
+//   err(a,k,b) = rel_err(d, max(s[a], s[k], s[b]))
 //   seg_err[a][d-2] = max_k err(a, k, a+d)
 // lx and s come from the host; the device runs + - * / fabs and comparisons only, in that order,
 // built without contraction, so a host restatement gives the same bits (ndpp_amd/thin.py).  The
@@ -34,6 +34,7 @@
 #include "../../include/ndpp_hip.h"
 #include "dev_util.h"
 #include "kernels.h"
+#include "section_util.h"
 
 namespace ndpp {
 namespace {
@@ -111,7 +112,7 @@ thin_partial_kernel(int n, int GL, int W, int A, int C, const int* __restrict__ 
         const double sa = sc[a], sk = sc[a0 + off[j]], sb = sc[b];
         double scale = sa > sk ? sa : sk;
         scale = sb > scale ? sb : scale;
-        const double e = !(dm[j] < INFINITY) ? INFINITY : (scale == 0.0 ? 0.0 : dm[j] / scale);
+        const double e = rel_err(dm[j], scale);
         res = e > res ? e : res;
       }
     }
@@ -156,14 +157,11 @@ int check_args(const char* who, int L, int G, int n, const double* x, const doub
   if (!y) return fail(NDPP_EINVAL, "%s: y is NULL", who);
   if (n_keep < 0) return fail(NDPP_EINVAL, "%s: n_keep=%d is negative", who, n_keep);
   if (n_keep > 0 && !tokeep) return fail(NDPP_EINVAL, "%s: tokeep is NULL with n_keep=%d", who, n_keep);
-  if ((long)G * L > INT_MAX / 2) return fail(NDPP_EINVAL, "%s: G * L = %ld does not fit an index", who, (long)G * L);
+  if (int rc = check_gl_index(who, G, L)) return rc;
   // bytes of the largest arrays: the rows, and the partial maxima (at most 280 per anchor)
   if ((size_t)n > SIZE_MAX / sizeof(double) / ((size_t)G * L) || (size_t)n > SIZE_MAX / sizeof(double) / 512)
     return fail(NDPP_EINVAL, "%s: n=%d rows of G * L = %ld overflow the byte count", who, n, (long)G * L);
-  for (int i = 0; i < n; ++i)
-    if (!(std::isfinite(x[i]) && x[i] > 0.0 && (i == 0 || x[i] > x[i - 1])))
-      return fail(NDPP_EINVAL, "%s: x[%d] = %.17g: x must be strictly increasing, positive and finite", who, i, x[i]);
-  return NDPP_OK;
+  return check_energy_grid(who, "x", n, x);
 }
 
 int segments(const char* who, int L, int G, int n, const double* x, const double* y, const double* y2,
@@ -228,9 +226,7 @@ int segments(const char* who, int L, int G, int n, const double* x, const double
     }
     hipLaunchKernelGGL(thin_fold_kernel, dim3(nblk((long)n * (W - 1), kThreads)), dim3(kThreads), 0, 0, n, W, C,
                        d_first.p, d_part.p, d_seg.p);
-    span.end();
-    NDPP_TRY(hipGetLastError());
-    NDPP_TRY(hipDeviceSynchronize());
+    NDPP_CLOSE_SPAN(span);
   }
   NDPP_TRY(d_seg.download(seg_err, (size_t)n * (W - 1)));
   return NDPP_OK;

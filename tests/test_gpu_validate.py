@@ -173,6 +173,32 @@ def test_random_rows_at_P10(hip):
     assert abs(s.negative - len(ref["negative"])) <= len(near_rows)
 
 
+def test_positivity_block_shapes_agree(hip):
+    """a row's result does not depend on where it sits: 1200 seeded rows as 2 E_in of 600 groups (a
+    group count above the block size: several passes of one block per E_in) and as 1200 E_in of one
+    group (64 E_in per block); P0 > 0 everywhere, so every row is in the band in both shapes"""
+    rng = np.random.default_rng(20261019)
+    L, M = 11, 21
+    flat = rng.standard_normal((1200, L)) * (0.2 / (np.arange(L) + 0.5))     # ~half the rows negative
+    flat[:, 0] = rng.uniform(0.5, 1.5, 1200)
+    sw, rw, minw, muw = hip.scatt_positivity(flat.reshape(2, 600, L), mu_points=M)
+    st, rt, mint, mut = hip.scatt_positivity(flat.reshape(1200, 1, L), mu_points=M)
+    print(f"block shapes: {sw.rows} rows, {sw.negative} negative, min {sw.min_value!r}")
+    assert sw.rows == st.rows == 1200 and sw.negative == st.negative and 0.2 < sw.negative / 1200 < 0.8
+    assert np.float64(sw.min_value).tobytes() == np.float64(st.min_value).tobytes()
+    assert (st.min_ein, st.min_group) == (sw.min_ein * 600 + sw.min_group, 0)
+    assert (rw[:, 0] * 600 + rw[:, 1]).tolist() == rt[:, 0].tolist() and not rt[:, 1].any()
+    assert minw.tobytes() == mint.tobytes() and muw.tobytes() == mut.tobytes()
+    # and the list is numpy's, except rows within the value tolerance of 0 (as test_random_rows_at_P10)
+    ref = np_positivity(flat.reshape(1200, 1, L), M)
+    near = np.abs(ref["all_min"]) <= TOL * ref["all_scale"]
+    near_rows = {tuple(r) for r in ref["all_rows"][near].tolist()}
+    got = [tuple(r) for r in rt.tolist() if tuple(r) not in near_rows]
+    want = [r for r in ref["negative"] if r not in near_rows]
+    assert got == want
+    assert abs(st.negative - len(ref["negative"])) <= len(near_rows)
+
+
 def test_repeatable_bits(hip):
     rng = np.random.default_rng(3)
     mat = rng.standard_normal((5000, 7, 11))
