@@ -149,6 +149,12 @@ struct FgBatch {
   const int* mu_nodes = nullptr;
   // ---- results
   double* raw;    // [n_jobs*R][G][L] per-call normalised moments
+  // ---- level 0: t_alias[5 n + slot] = the task record of an earlier live task of the same job whose
+  // E_out is the very same double -- consecutive segments share their ends (fg_setup_group) --, which
+  // is integrated in its place; -1 = the task is integrated itself.  null = off.  The prep stage
+  // flags an aliased task in t_gl (kGaussAlias) as one whose rows are all done, which is how the
+  // sort weight, the walk and the combine come to leave it alone: the table needs t_gl.
+  int* t_alias = nullptr;
 
   NDPP_HD double A_of(int job) const { return job_A ? job_A[job] : A; }
   NDPP_HD double kT_of(int job) const { return job_kT ? job_kT[job] : kT; }
@@ -184,6 +190,7 @@ struct FgBatch {
     for (int r = 0; r < R; ++r) m |= ((1u << L) - 1u) << (r * kRowBits);
     return m;
   }
+  NDPP_HD int alias_of(int level, int rec) const { return (level == 0 && t_alias && t_gl) ? t_alias[rec] : -1; }
   NDPP_HD int node_job(int n) const { return node_info[4 * n + 2] & 0x3ffffff; }
   NDPP_HD int node_depth(int n) const { return node_info[4 * n + 2] >> 26; }
 };
@@ -196,7 +203,8 @@ struct FgBatch {
 // A slot that the reference does not integrate, or integrates over a
 // zero-width interval (value exactly 0), gets mask 0.
 // -----------------------------------------------------------------------------
-NDPP_HD void fg_setup_group(const FgBatch& B, int job, int g) {
+// the segments of (job, g): ends sa, sb and live[s] = integrated over a non-empty interval
+NDPP_HD void fg_group_layout(const FgBatch& B, int job, int g, double* sa, double* sb, bool* live) {
   const double Ein = B.job_ein[job];
   const double A = B.A_of(job), kT = B.kT_of(job);
   double alphaEin = (A - 1.0) / (A + 1.0);
@@ -205,7 +213,6 @@ NDPP_HD void fg_setup_group(const FgBatch& B, int job, int g) {
   fg_eout_bounds(A, kT, Ein, Eout_lo, Eout_hi);
   const double eg = B.e_bins[g], eg1 = B.e_bins[g + 1];
 
-  double sa[kSegPerGroup], sb[kSegPerGroup];
   bool on[kSegPerGroup] = {false, false, false, false, false};
   if ((eg < Eout_hi) && (eg1 > Eout_lo)) {
     double Elo = (Eout_lo > eg) ? Eout_lo : eg;
@@ -225,18 +232,67 @@ NDPP_HD void fg_setup_group(const FgBatch& B, int job, int g) {
   } else {
     sa[4] = eg; sb[4] = eg1; on[4] = true;  // freegas.F90:126-130
   }
+  for (int s = 0; s < kSegPerGroup; ++s) live[s] = on[s] && (sa[s] != sb[s]);
+}
+// the root slots of a group in the order of their E_out: consecutive live ones share an end
+NDPP_HD int fg_chain_slot(int k) {
+  constexpr int chain[kSegPerGroup] = {0, 2, 3, 4, 1};
+  return chain[k];
+}
+
+// the very same double (0.0 and -0.0 are not: the tasks' inputs must agree bit for bit)
+NDPP_HD bool same_bits(double x, double y) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __double_as_longlong(x) == __double_as_longlong(y);
+#else
+  long long a, b;
+  __builtin_memcpy(&a, &x, sizeof a);
+  __builtin_memcpy(&b, &y, sizeof b);
+  return a == b;
+#endif
+}
+
+NDPP_HD void fg_setup_group(const FgBatch& B, int job, int g) {
+  double sa[kSegPerGroup], sb[kSegPerGroup];
+  bool live[kSegPerGroup];
+  fg_group_layout(B, job, g, sa, sb, live);
   const unsigned full = B.full_mask();
   const int nch = B.nch();
   for (int s = 0; s < kSegPerGroup; ++s) {
     int n = (job * B.G + g) * kSegPerGroup + s;
-    bool live = on[s] && (sa[s] != sb[s]);
-    B.node_a[n] = live ? sa[s] : 0.0;
-    B.node_b[n] = live ? sb[s] : 0.0;
-    B.node_info[4 * n + 0] = live ? (int)full : 0;
+    B.node_a[n] = live[s] ? sa[s] : 0.0;
+    B.node_b[n] = live[s] ? sb[s] : 0.0;
+    B.node_info[4 * n + 0] = live[s] ? (int)full : 0;
     B.node_info[4 * n + 1] = -1;
     B.node_info[4 * n + 2] = job;  // depth 0
     B.node_info[4 * n + 3] = 0;
     for (int ch = 0; ch < nch; ++ch) B.S(ch, n) = 0.0;
+  }
+  if (!B.t_alias) return;
+  // The lower end (point slot 0) of a live segment that starts at the very double at which the live
+  // segment before it ends (point slot 4) is that task over again: same job, same E_out, same
+  // inputs to every stage.  The segment before the group's first is the last one of the group
+  // below (of the nearest group below that has one: a group of zero width has none).  A source is
+  // an upper end, an alias a lower end: no chains.
+  const int root = (job * B.G + g) * kSegPerGroup;
+  for (int k = 0; k < 5 * kSegPerGroup; ++k) B.t_alias[5 * root + k] = -1;
+  int prev = -1;            // node of the live segment before
+  double prev_b = 0.0;
+  // (the layout of the group below is worked out a second time here, and of more groups where groups
+  // of zero width lie in between: the price of needing no pass of its own after the set-up)
+  for (int gp = g - 1; gp >= 0 && prev < 0; --gp) {
+    double pa[kSegPerGroup], pb[kSegPerGroup];
+    bool pl[kSegPerGroup];
+    fg_group_layout(B, job, gp, pa, pb, pl);
+    for (int k = 0; k < kSegPerGroup; ++k)
+      if (pl[fg_chain_slot(k)]) { prev = root - (g - gp) * kSegPerGroup + fg_chain_slot(k); prev_b = pb[fg_chain_slot(k)]; }
+  }
+  for (int k = 0; k < kSegPerGroup; ++k) {
+    const int s = fg_chain_slot(k);
+    if (!live[s]) continue;
+    if (prev >= 0 && same_bits(prev_b, sa[s])) B.t_alias[5 * (root + s) + 0] = 5 * prev + 4;
+    prev = root + s;
+    prev_b = sb[s];
   }
 }
 
@@ -352,6 +408,7 @@ NDPP_HD bool fg_gauss_box(int mu_its, double mu_tol) {
 }
 // Is the inner integral of this pair in the zone the Gauss rule may take (mu_gauss_task below)?
 constexpr unsigned kGaussNear = 0x80u;     // t_gl flag (prep -> Gauss stage): a "near" candidate
+constexpr unsigned kGaussAlias = 0x40u;    // t_gl flag: not a candidate, a level-0 alias (FgBatch::t_alias); its rows read "done"
 NDPP_HD unsigned fg_gauss_zone(const FgBatch& B, const FgPair& q, double Ein, double Eout) {
   const double amin = (q.EpE - 2.0 * q.s2) / q.AkT;
   if (!(amin >= B.gl_amin)) return 0u;
@@ -367,6 +424,10 @@ NDPP_HD void fg_prep_task(const FgBatch& B, int level, int base, int t) {
   else { n = base + (t >> 1); slot = 1 + 2 * (t & 1); }
   if (B.node_info[4 * n + 0] == 0) {
     if (B.t_gl) B.t_gl[t] = 0;
+    return;
+  }
+  if (B.alias_of(level, t) >= 0) {      // its source is prepared and integrated: every row is done
+    B.t_gl[t] = (unsigned char)(kGaussAlias | ((1u << B.R) - 1u));
     return;
   }
   const int job = B.node_job(n);
@@ -651,7 +712,7 @@ NDPP_HD int gauss_next_phase(const FgBatch& B, int p, unsigned st) {
 template <int R>
 NDPP_HD unsigned mu_gauss_entry(const FgBatch& B, int level, int base, int t) {
   unsigned rows = B.t_gl[t];
-  if (!rows) return 0;
+  if (!rows || (rows & kGaussAlias)) return 0;
   const unsigned near = rows & kGaussNear;
   rows &= ~kGaussNear;
   const int n_node = level == 0 ? t / 5 : base + (t >> 1);
@@ -1247,6 +1308,17 @@ NDPP_HD void fg_node_process(const FgBatch& B, int level, int base, int i) {
   const unsigned mask = (unsigned)B.node_info[4 * n + 0];
   if (mask == 0) return;
   const int depth = B.node_depth(n);
+  if (level == 0 && B.t_alias) {
+    // an aliased lower end takes the values of its source, an upper end of another root: this thread
+    // alone writes F(0, ., n), and no kernel writes a source's F(4, ., .) any more
+    const int src = B.t_alias[5 * n + 0];
+    if (src >= 0) {
+      const int sn = src / 5, ss = src - 5 * sn;
+      for (int r = 0; r < B.R; ++r)
+        for (int l = 0; l < B.L; ++l)
+          if (mask & chan_bit(r, l)) B.F(0, r * B.L + l, n) = B.F(ss, r * B.L + l, sn);
+    }
+  }
   const double a = B.node_a[n], b = B.node_b[n];
   const double c = 0.5 * (a + b);
   const double h = b - a;

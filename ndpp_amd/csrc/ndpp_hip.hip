@@ -562,6 +562,7 @@ struct FgTunables {
   long max_chunk_ein = 0;      // forces overflow -> halve the chunk).  MAX_CHUNK_EIN > 0: caps a chunk (test hook)
   bool split = true;           // NO_SPLIT=1: off.  The split walk (fg_pipeline.h kSplitLog2) on small levels ...
   double split_x = 32.0;       // SPLIT_BELOW_X: ... those with at most this many inner integrals per lane
+  bool alias = true;           // NO_ALIAS=1: off.  A level-0 E_out shared by two segments is integrated once (FgBatch::t_alias)
   bool gauss = true;           // GAUSS=0: off, every inner integral goes to the adaptive walk
   bool gauss_phased = true;    // GAUSS_PHASED=0: the Gauss stage one candidate per lane, not by phases
   bool sort = true;            // NO_SORT=1: off, the walk takes a level's tasks in creation order (test hook)
@@ -582,6 +583,7 @@ FgTunables read_fg_tunables(int G) {
   if ((e = getenv("NDPP_HIP_MAX_CHUNK_EIN")) && atol(e) > 0) t.max_chunk_ein = atol(e);
   t.split = !first_is("NDPP_HIP_NO_SPLIT", '1');
   if ((e = getenv("NDPP_HIP_SPLIT_BELOW_X"))) t.split_x = atof(e);
+  t.alias = !first_is("NDPP_HIP_NO_ALIAS", '1');
   t.gauss = !first_is("NDPP_HIP_GAUSS", '0');
   t.gauss_phased = !first_is("NDPP_HIP_GAUSS_PHASED", '0');
   t.sort = !first_is("NDPP_HIP_NO_SORT", '1');
@@ -663,10 +665,12 @@ int plan_batch(const ndpp_params* p, int n_ein, int n_rows, int G, int rows_per_
   pl.fixed = (size_t)n_ein * 3 * sizeof(int) + (size_t)n_rows * sizeof(int) + (1u << 20) +
              sizeof(int) * ((size_t)1 << L) + pl.contexts * pl.ctx_fixed + 4096;
   const size_t node_bytes = bytes_per_node(pl.nch);
+  // job records + raw row + the level-0 alias table (FgBatch::t_alias: 5 records for each of a job's 5 G roots)
+  const size_t per_job_bytes = sizeof(double) * (GL + 3) + sizeof(int) * 2 + 16 + sizeof(int) * 25 * (size_t)G;
   // What the whole batch would take in one chunk.  If the cached workspace already holds that,
   // the free-memory query (~0.1 ms; thousands of small calls in a library-shaped run) is skipped.
   const size_t whole = pl.fixed + ((size_t)n_ein + pl.contexts * pl.spare_ein) * pl.nodes_per_ein * node_bytes +
-                       (size_t)n_ein * rows_per_ein * (sizeof(double) * (GL + 3) + sizeof(int) * 2 + 16) + 4096;
+                       (size_t)n_ein * rows_per_ein * per_job_bytes + 4096;
   size_t budget;
   if (g_ws.base && whole <= g_ws.bytes) {
     budget = g_ws.bytes;
@@ -676,7 +680,6 @@ int plan_batch(const ndpp_params* p, int n_ein, int n_rows, int G, int rows_per_
     if (g_ws.base) free_b += g_ws.bytes;
     budget = std::min<size_t>((size_t)(free_b * 0.6), (size_t)128 << 30);
   }
-  const size_t per_job_bytes = sizeof(double) * (GL + 3) + sizeof(int) * 2 + 16;  // job records + raw row
   // the arena holds ncap nodes; a chunk takes ncap / nodes_per_ein energies
   size_t ncap = (budget > pl.fixed ? budget - pl.fixed : 0) /
                 (node_bytes + (per_job_bytes * rows_per_ein + pl.nodes_per_ein - 1) / pl.nodes_per_ein);
@@ -916,6 +919,8 @@ int carve_contexts(std::vector<FgCtx>& ctx, bool side_by_side, const BatchCall& 
     // contexts only, and only when the batch's tables were looked at (a context of the product
     // arithmetic then holds energies of rows linear in mu only)
     B.t_gl = (gauss_on && !c.strict) ? cv.take<unsigned char>(B.tcap) : nullptr;
+    // (aliases are flagged in t_gl, FgBatch::t_alias; one entry per level-0 task record of the chunk's jobs)
+    B.t_alias = (t.alias && B.t_gl) ? cv.take<int>((size_t)25 * a.G * max_jobs) : nullptr;
     B.job_ein = c.job_ein = cv.take<double>(max_jobs);
     B.job_row = c.job_row = cv.take<int>(max_jobs);
     c.job_A = cv.take<double>(max_jobs); c.job_kT = cv.take<double>(max_jobs);
