@@ -720,6 +720,61 @@ int ndpp_scatt_minimum_evals(int n_ein, int G, int L, const double *mat, int n_m
                              double *lo, double *hi, double *mu_at, int *cls, int *evals /* [n_ein][G] */,
                              ndpp_minimum *summary);
 
+/* ---- repair of negative rows, certified positive.  Replaces nothing: the
+ * reference never repairs a row.  A row has stored moments a_0 .. a_{L-1} and
+ * f(mu) = sum (l + 1/2) a_l P_l(mu).  The repaired row is a_l * w_l(t) with one parameter t in [0, 1],
+ * in one of two families:
+ *   heat     w_l = t^(l(l+1)/2): the heat kernel on the sphere, e^(-tau l(l+1)) with t = e^(-2 tau), a
+ *            non-negative smoothing kernel; it damps what truncation produced (high orders) far more
+ *            than P1;
+ *   uniform  w_0 = 1, w_l = t for l >= 1: the blend towards the isotropic row with the same P0.
+ * In both w_0 = 1 (P0 is untouched bit for bit, hence the band gmin..gmax, sum_g P0, print_tol and
+ * condensation), P1 is kept to exactly the fraction t, t = 1 is the identity and t = 0 gives
+ * f = a_0 / 2, positive when a_0 > 0: a passing t always exists.
+ * Weights, by multiplications only and in this order (host and device give the same bits; no exp or
+ * pow on the device): heat  p = t; w_1 = t; for l = 2 .. L-1: p = p * t; w_l = w_{l-1} * p;  uniform
+ * w_l = t;  repaired moment a_l * w_l (a_0 itself for l = 0).
+ * Search: bisection on t with exactly `steps` trips (1..52).  Invariant: t_pass (initially 0) passes
+ * and t_fail (initially 1) fails; each trip tests the exact dyadic midpoint and moves one end; the
+ * result is t_pass.  A value t PASSES when ndpp_scatt_minimum's search of one row, at rel_tol and
+ * n_moments = L, classes the row a_l * w_l(t) NDPP_MIN_POSITIVE (NDPP_MIN_UNSETTLED may be set: lo >= 0
+ * is valid either way); NDPP_MIN_UNDECIDED counts as failing.  Positivity is not assumed monotone in t:
+ * the invariant alone makes the result certified, and t + 2^-steps is a value that was seen to fail.
+ * No loop depends on convergence: at most steps trips, each bounded by NDPP_MIN_MAX_EVALS.
+ * mode: NDPP_REPAIR_HEAT, NDPP_REPAIR_UNIFORM, or NDPP_REPAIR_BEST: both searches, the one with the
+ * larger t is kept, uniform on a tie (when t_uniform >= t_heat the uniform row keeps at least as much
+ * of every moment as the heat row; otherwise heat keeps more of P1).
+ * Rows: those ndpp_scatt_minimum examines at n_moments = L -- per E_in the groups gmin..gmax, the first
+ * and last with P0 > 0, interior rows included.  A row whose class at t = 1 is NEGATIVE is repaired;
+ * an UNDECIDED one only when undecided != 0.  Of these, a row with a_0 == 0 becomes the zero row
+ * (t = 0, no search) and a row with a_0 < 0 is UNREPAIRABLE: copied unchanged and counted.  A
+ * non-finite row is copied unchanged and counted.  Everything else, entries outside the band
+ * included, is copied bit for bit.
+ * how: -1 not examined, 0 untouched, 1 heat, 2 uniform, 3 unrepairable, 4 non-finite.  t: the
+ * parameter of a repaired row, 1.0 where untouched (how 0, 3, 4), -1.0 where not examined.
+ * The classes are found on the device with the matrix kept there; the rows to repair are listed on
+ * the host in (iE, g) order, and the summary is folded there in that order.  ndpp_last_gpu_ms()
+ * after the call is the time of the repair kernel (of the classification when no row was listed).
+ * NDPP_EINVAL, decided before the device is touched: L outside 1..NDPP_MAX_ORDER, G < 1, n_ein < 0,
+ * an unknown mode, steps outside 1..52, rel_tol negative, NaN or infinite, a NULL pointer, sizes
+ * whose bytes overflow.  n_ein = 0 is an empty, successful call.  Without a device NDPP_EDEVICE.    */
+#define NDPP_REPAIR_BEST    0
+#define NDPP_REPAIR_HEAT    1
+#define NDPP_REPAIR_UNIFORM 2
+typedef struct ndpp_repair {
+  long   rows, repaired, heat, uniform, unrepairable, nonfinite;  /* rows: examined; repaired = heat + uniform */
+  double min_t;               /* smallest t over the repaired rows; 1.0 if none */
+  int    min_ein, min_group;  /* first row in (iE, g) order attaining it; none: -1, -1 */
+} ndpp_repair;
+int ndpp_scatt_repair(int n_ein, int G, int L, const double *mat /* [n_ein][G][L] */, int mode, int steps,
+                      int undecided, double rel_tol, double *out /* [n_ein][G][L] */,
+                      double *t /* [n_ein][G] */, int *how /* [n_ein][G] */, ndpp_repair *summary);
+/* the same call, which also returns the evaluations of f each repaired row made in its searches (0
+ * elsewhere): for measurements (tools/bench_repair.py).  NULL evals: NDPP_EINVAL.                 */
+int ndpp_scatt_repair_evals(int n_ein, int G, int L, const double *mat, int mode, int steps, int undecided,
+                            double rel_tol, double *out, double *t, int *how, int *evals /* [n_ein][G] */,
+                            ndpp_repair *summary);
+
 /* ---- interpolation error of an incoming-energy grid.  Replaces nothing: the reference never
  * measures it (thin_grid compares stored rows with each other, never with a fresh one).
  * x[n] with rows y[n][G][L]; x_mid[n-1] with rows y_mid[n-1][G][L] integrated there.  For

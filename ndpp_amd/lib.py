@@ -47,7 +47,7 @@ EXPORTS = [
     "ndpp_elastic_tab_batch", "ndpp_file6_tab_batch", "ndpp_law9_tab_batch", "ndpp_scatt_nuclide_tab",
     "ndpp_scatt_library_tab", "ndpp_scatt_library_at", "ndpp_grid_error",
     "ndpp_thin_segments", "ndpp_thin_bounded", "ndpp_lib_compare",
-    "ndpp_scatt_minimum", "ndpp_scatt_minimum_evals",
+    "ndpp_scatt_minimum", "ndpp_scatt_minimum_evals", "ndpp_scatt_repair", "ndpp_scatt_repair_evals",
 ]
 
 
@@ -328,6 +328,22 @@ class Minimum(C.Structure):
 # ndpp_scatt_minimum: classes (low two bits of cls), the unsettled bit and the cap on evaluations per row
 MIN_POSITIVE, MIN_UNDECIDED, MIN_NEGATIVE, MIN_NONFINITE, MIN_UNSETTLED = 0, 1, 2, 3, 4
 MIN_MAX_EVALS = 16384
+
+
+
+class Repair(C.Structure):
+    """ndpp_repair: the summary of one ndpp_scatt_repair call."""
+    _fields_ = [("rows", C.c_long), ("repaired", C.c_long), ("heat", C.c_long), ("uniform", C.c_long),
+                ("unrepairable", C.c_long), ("nonfinite", C.c_long), ("min_t", C.c_double),
+                ("min_ein", C.c_int), ("min_group", C.c_int)]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+# ndpp_scatt_repair: the modes, and the values of `how`
+REPAIR_BEST, REPAIR_HEAT, REPAIR_UNIFORM = 0, 1, 2
+HOW_UNEXAMINED, HOW_UNTOUCHED, HOW_HEAT, HOW_UNIFORM, HOW_UNREPAIRABLE, HOW_NONFINITE = -1, 0, 1, 2, 3, 4
 
 FMT_ASCII, FMT_BINARY, FMT_HDF5, FMT_NONE, FMT_HUMAN = 1, 2, 3, 4, 5
 # per-E_in status bits (include/ndpp_hip.h NDPP_ST_*)
@@ -613,6 +629,11 @@ def load(build_if_missing: bool = False, torch_compat: bool | None = None) -> C.
         lib.ndpp_scatt_minimum_evals.argtypes = [C.c_int, C.c_int, C.c_int, c_double_p, C.c_int, C.c_double,
                                                  c_double_p, c_double_p, c_double_p, c_int_p, c_int_p,
                                                  C.POINTER(Minimum)]
+        lib.ndpp_scatt_repair.argtypes = [C.c_int, C.c_int, C.c_int, c_double_p, C.c_int, C.c_int, C.c_int,
+                                          C.c_double, c_double_p, c_double_p, c_int_p, C.POINTER(Repair)]
+        lib.ndpp_scatt_repair_evals.argtypes = [C.c_int, C.c_int, C.c_int, c_double_p, C.c_int, C.c_int, C.c_int,
+                                                C.c_double, c_double_p, c_double_p, c_int_p, c_int_p,
+                                                C.POINTER(Repair)]
     _lib = lib
     return lib
 
@@ -1179,6 +1200,28 @@ def scatt_minimum(mat, n_moments=None, rel_tol=1e-10, want_evals=False):
     _check(load().ndpp_scatt_minimum(n, G, L, _dp(mat), nm, float(rel_tol), _dp(lo), _dp(hi), _dp(mu_at), _ip(cls),
                                      C.byref(s)))
     return s, lo, hi, mu_at, cls
+
+
+def scatt_repair(mat, mode=REPAIR_BEST, steps=20, undecided=False, rel_tol=1e-10, want_evals=False):
+    """ndpp_scatt_repair on one dense section mat[n_ein][G][L]: every row ndpp_scatt_minimum classes
+    NEGATIVE (UNDECIDED too when `undecided`) becomes a_l * w_l(t), t the largest value of a
+    `steps`-trip bisection whose filtered row is certified POSITIVE at rel_tol (the rules are in
+    include/ndpp_hip.h).  mode: REPAIR_BEST / REPAIR_HEAT / REPAIR_UNIFORM.  Returns (Repair summary,
+    out (n_ein, G, L), t (n_ein, G), how (n_ein, G) int32: HOW_*).  want_evals: also the evaluations of
+    f each repaired row made, (n_ein, G) int32, as a fifth value."""
+    mat = _f64(mat)
+    if mat.ndim != 3:
+        raise ValueError(f"mat must be (n_ein, G, L), got shape {mat.shape}")
+    n, G, L = mat.shape
+    out, t, how = np.zeros((n, G, L)), np.full((n, G), -1.0), np.full((n, G), -1, np.int32)
+    s = Repair()
+    args = (n, G, L, _dp(mat), int(mode), int(steps), int(bool(undecided)), float(rel_tol), _dp(out), _dp(t), _ip(how))
+    if want_evals:
+        evals = np.zeros((n, G), np.int32)
+        _check(load().ndpp_scatt_repair_evals(*args, _ip(evals), C.byref(s)))
+        return s, out, t, how, evals
+    _check(load().ndpp_scatt_repair(*args, C.byref(s)))
+    return s, out, t, how
 
 
 def expand_moments(moments, n_moments=None, mu_points=201):

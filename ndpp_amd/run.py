@@ -42,7 +42,24 @@ input error):
                        2..64).  Group edges, the free-gas cutoff and the reaction thresholds are
                        kept.  Thermal tables and chi grids are not thinned.  With --check-grid the
                        thinned grids are what is checked.  `thinning_tol` of ndpp.xml -- the
-                       reference's rule, the thin_tol of the file header -- is independent of it."""
+                       reference's rule, the thin_tol of the file header -- is independent of it.
+
+Positivity (ndpp_amd.repair; Legendre output only):
+  --repair-positivity  the last step before a table's file is formed, after print_tol and thinning:
+                       every row whose certified minimum (`validate --certified`) is negative is
+                       replaced by a_l * w_l(t), the largest t of a bisection whose row is certified
+                       positive.  The certified rows are exactly the rows
+                       written; P0, the grids and gmin / gmax do not change; the file header is the
+                       reference's and carries no mark.  One line per table and section is printed
+                       and the report goes under "repair" in --json.  The figures of --check-grid,
+                       --refine-grid and --thin-grid refer to the unrepaired rows: the report's
+                       largest change is what the user adds to them.  scatt_type tabular is an input
+                       error (bins are non-negative already).
+  --repair-mode M      best (default: the family that keeps more), heat or uniform
+  --repair-steps N     bisection steps, 1..52 (default 20): t is within 2^-N of a failing value
+  --repair-rel-tol X   the certificate's tolerance, finite and >= 0 (default 1e-10)
+  --repair-undecided   also repair rows whose minimum is within the tolerance of zero
+                       Each of the four is an input error without --repair-positivity."""
 from __future__ import annotations
 
 import argparse
@@ -56,7 +73,7 @@ from pathlib import Path
 
 import numpy as np
 
-from . import ace, grid, gridcheck, lib, thin
+from . import ace, grid, gridcheck, lib, repair, thin
 
 EXIT_OK, EXIT_INPUT, EXIT_LIBRARY = 0, 2, 3
 
@@ -287,15 +304,25 @@ def _device_ms() -> float:
     return float(sum(lib.profile_get().values()))
 
 
-def compute(s: dict, tables: list, grid_opts: dict | None = None) -> tuple:
+def compute(s: dict, tables: list, grid_opts: dict | None = None, repair_opts: dict | None = None) -> tuple:
     """Every table's file bytes, its timing record and the grid report: ([(file name, bytes)],
     [record], report).  The report is None without grid_opts (check, check_tol, refine_tol,
-    max_passes, max_growth, thin_tol, thin_window)."""
+    max_passes, max_growth, thin_tol, thin_window).  With repair_opts (mode, steps, rel_tol,
+    undecided) every table's finished rows are repaired before its file is formed and a fourth value
+    is returned: [dict(name, kind, report)] per table."""
     p, o, bins = params_of(s), options_of(s), s["energy_bins"]
     tab = s["scatt_type"] == "tabular"
     files, recs = [None] * len(tables), [None] * len(tables)
     go = grid_opts or {}
     raw, grid_rep = [None] * len(tables), None
+    repair_rep = [None] * len(tables)
+
+    def finish(k, result):
+        fin, _ = lib.finish_scatt(o, result, bins)
+        if repair_opts is not None:
+            fin, rr = repair.repair_result(fin, **repair_opts)
+            repair_rep[k] = dict(name=tables[k]["listing"]["name"], kind=tables[k]["kind"], report=rr)
+        return fin
     neut = [k for k, t in enumerate(tables) if t["kind"] == "neutron"]
     if neut:
         lib.profile_reset()
@@ -339,7 +366,7 @@ def compute(s: dict, tables: list, grid_opts: dict | None = None) -> tuple:
                 chi = (e_chi, ct, cp, cd)
                 chi_rec = dict(energies=len(e_chi), wall_s=time.perf_counter() - c0, device_ms=_device_ms(),
                                last_gpu_ms=float(lib.load().ndpp_last_gpu_ms()))
-            fin, _ = lib.finish_scatt(o, r, bins)
+            fin = finish(k, r)
             if s["lib_format"] != lib.FMT_NONE:
                 files[k] = lib.nuclide_file(o, t["data"]["name"], t["data"]["kT"], fin, bins, chi=chi)
             recs[k] = dict(name=t["listing"]["name"], kind="neutron", file=t["file"],
@@ -357,8 +384,7 @@ def compute(s: dict, tables: list, grid_opts: dict | None = None) -> tuple:
         mat = lib.sab_batch(p, d, ein, bins)
         wall, dev, last = time.perf_counter() - t0, _device_ms(), float(lib.load().ndpp_last_gpu_ms())
         raw[k] = dict(ein_el=ein, el_mat=mat, ein_inel=None, inel_mat=None, nuinel_mat=None)
-        fin, _ = lib.finish_scatt(o, dict(ein_el=ein, el_mat=mat, ein_inel=None, inel_mat=None, nuinel_mat=None),
-                                  bins)
+        fin = finish(k, dict(ein_el=ein, el_mat=mat, ein_inel=None, inel_mat=None, nuinel_mat=None))
         if s["lib_format"] != lib.FMT_NONE:
             files[k] = lib.nuclide_file(o, d["name"], d["kT"], fin, bins, is_sab=True)
         recs[k] = dict(name=t["listing"]["name"], kind="thermal", file=t["file"],
@@ -368,6 +394,8 @@ def compute(s: dict, tables: list, grid_opts: dict | None = None) -> tuple:
         t1 = time.perf_counter()
         rep = gridcheck.check(p, bins, tables, raw, s["nuscatter"], go["check_tol"])
         grid_rep = dict(grid_rep or {}, check=dict(tol=go["check_tol"], wall_s=time.perf_counter() - t1, tables=rep))
+    if repair_opts is not None:
+        return out, recs, grid_rep, repair_rep
     return out, recs, grid_rep
 
 
@@ -421,7 +449,8 @@ def write_library(run_dir, files: list, xml: bytes) -> list:
     return [p for p, _ in items]
 
 
-def run(run_dir, json_path=None, out=sys.stdout, grid_opts: dict | None = None) -> int:
+def run(run_dir, json_path=None, out=sys.stdout, grid_opts: dict | None = None,
+        repair_opts: dict | None = None) -> int:
     """The whole driver; returns the exit status."""
     run_dir = Path(run_dir)
     t_start = time.perf_counter()
@@ -431,6 +460,9 @@ def run(run_dir, json_path=None, out=sys.stdout, grid_opts: dict | None = None) 
             raise InputError("--check-grid, --refine-grid and --thin-grid cover Legendre output only: the tabular rows of the "
                              "free-gas range do not settle, so an error measured on them would be the "
                              "quadrature's, not the grid's.")
+        if repair_opts is not None and s["scatt_type"] == "tabular":
+            raise InputError("--repair-positivity covers Legendre output only: the bins of tabular output are "
+                             "non-negative already.")
         xs = read_cross_sections(s["cross_sections"])
         tables = load_tables(s, xs)
         if not tables:
@@ -445,7 +477,11 @@ def run(run_dir, json_path=None, out=sys.stdout, grid_opts: dict | None = None) 
         except InputError as e:
             print(f"ndpp_amd.run: input error: {e}", file=sys.stderr)
             return EXIT_INPUT
-        files, recs, grid_rep = compute(s, tables, grid_opts)
+        repair_rep = None
+        if repair_opts is not None:
+            files, recs, grid_rep, repair_rep = compute(s, tables, grid_opts, repair_opts)
+        else:
+            files, recs, grid_rep = compute(s, tables, grid_opts)
         xml = lib_xml_of(s, run_dir, tables)
     except (lib.NdppError, RuntimeError, OSError) as e:
         print(f"ndpp_amd.run: library error: {e}", file=sys.stderr)
@@ -472,10 +508,17 @@ def run(run_dir, json_path=None, out=sys.stdout, grid_opts: dict | None = None) 
     if grid_rep and "check" in grid_rep:
         for line in gridcheck.format_lines(grid_rep["check"]["tables"]):
             print(line, file=out)
+    if repair_rep is not None:
+        for t in repair_rep:
+            for line in repair.format_lines(t["name"], t["report"]):
+                print(line, file=out)
     if json_path:
         rec = dict(run_dir=str(run_dir), wall_s=total, scatt_type=s["scatt_type"], tables=recs)
         if grid_opts is not None:
             rec["grid"] = grid_rep
+        if repair_rep is not None:
+            rec["repair"] = dict(repair_opts, tables=[dict(name=t["name"], kind=t["kind"], **t["report"].as_dict())
+                                                      for t in repair_rep])
         Path(json_path).write_text(json.dumps(rec, indent=1) + "\n")
     return EXIT_OK
 
@@ -512,6 +555,24 @@ def _grid_options(a):
                 max_growth=a.max_growth, thin_tol=thin_tol, thin_window=window)
 
 
+def _repair_options(a):
+    """The repair flags as compute()'s repair_opts (None: --repair-positivity not given).  Raises InputError."""
+    given = [f for f, v in (("--repair-mode", a.repair_mode), ("--repair-steps", a.repair_steps),
+                            ("--repair-rel-tol", a.repair_rel_tol), ("--repair-undecided", a.repair_undecided or None))
+             if v is not None]
+    if not a.repair_positivity:
+        if given:
+            raise InputError(f"{', '.join(given)}: a setting of --repair-positivity; give that flag too")
+        return None
+    steps = 20 if a.repair_steps is None else a.repair_steps
+    rel_tol = 1e-10 if a.repair_rel_tol is None else a.repair_rel_tol
+    try:
+        repair.check_options(steps, rel_tol)
+    except ValueError as e:
+        raise InputError(str(e)) from None
+    return dict(mode=a.repair_mode or "best", steps=steps, rel_tol=rel_tol, undecided=bool(a.repair_undecided))
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(prog="python -m ndpp_amd.run",
                                  description="Build an NDPP library from <dir>/ndpp.xml and the ACE tables its "
@@ -533,13 +594,24 @@ def main(argv=None) -> int:
                          "neighbours reproduces to TOL")
     ap.add_argument("--thin-window", metavar="W", type=int, default=None,
                     help="points one thinned segment may span, 2..64 (default 32)")
+    ap.add_argument("--repair-positivity", action="store_true",
+                    help="replace every row whose certified minimum is negative by a filtered row that is "
+                         "certified positive (Legendre output only)")
+    ap.add_argument("--repair-mode", choices=sorted(repair.MODES), default=None,
+                    help="filter family: best (default), heat or uniform")
+    ap.add_argument("--repair-steps", metavar="N", type=int, default=None, help="bisection steps, 1..52 (default 20)")
+    ap.add_argument("--repair-rel-tol", metavar="X", type=float, default=None,
+                    help="tolerance of the certificate, finite and >= 0 (default 1e-10)")
+    ap.add_argument("--repair-undecided", action="store_true",
+                    help="also repair rows whose minimum is within the tolerance of zero")
     a = ap.parse_args(argv)
     try:
         grid_opts = _grid_options(a)
+        repair_opts = _repair_options(a)
     except InputError as e:
         print(f"ndpp_amd.run: input error: {e}", file=sys.stderr)
         return EXIT_INPUT
-    return run(a.run_dir, a.json, grid_opts=grid_opts)
+    return run(a.run_dir, a.json, grid_opts=grid_opts, repair_opts=repair_opts)
 
 
 if __name__ == "__main__":

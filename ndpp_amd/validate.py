@@ -38,6 +38,10 @@ error (or when the check cannot run: no device).  With --certified [--rel-tol 1e
 tables go through `minimum` (tabular ones keep tab_positivity): exit 1 if any row is negative or
 non-finite; undecided and unsettled rows are counted and printed and do not fail the run.
 --certified does not go together with --mu-points (exit 2).
+--certified --repair-report adds to each section's line what `python -m ndpp_amd.run
+--repair-positivity` would do to it (ndpp_amd.repair, defaults: rows by family, smallest t, largest
+change); nothing is written and the exit status stays that of --certified.  Without --certified, or
+with --moments (the repair acts on the stored rows, all moments), it is an input error (exit 2).
 """
 from __future__ import annotations
 
@@ -332,7 +336,7 @@ def _print_report(name: str, t: reader.NdppTable, rep: Report, out) -> None:
             print(f"      ... {s.negative - 10} more", file=out)
 
 
-def _print_minimum(name: str, t: reader.NdppTable, rep: MinimumReport, out) -> None:
+def _print_minimum(name: str, t: reader.NdppTable, rep: MinimumReport, out, repair_rep=None) -> None:
     status = "positive" if rep.positive else "NEGATIVE"
     print(f"{name}: {status}  (P{t.scatt_order}, {t.groups} groups, {rep.n_moments} moments, certified, "
           f"rel tol {rep.rel_tol:g})", file=out)
@@ -346,6 +350,13 @@ def _print_minimum(name: str, t: reader.NdppTable, rep: MinimumReport, out) -> N
             print(f"      E_in {iE + 1:6d} ({_ein(t, sec, iE):.6e} MeV)  group {g + 1:4d}  {what}", file=out)
         if s.negative + s.nonfinite > 10:
             print(f"      ... {s.negative + s.nonfinite - 10} more", file=out)
+        if repair_rep is not None and sec in repair_rep.sections:
+            r = repair_rep.sections[sec]
+            what = (f", smallest t {r.min_t:.6f} at E_in {r.min_ein + 1}, group {r.min_group + 1}, largest change "
+                    f"{r.max_change:.3e}" if r.repaired else "")
+            print(f"      a repair ({repair_rep.mode}, {repair_rep.steps} steps) would change {r.repaired} rows: heat "
+                  f"{r.heat}, uniform {r.uniform}; unrepairable {r.unrepairable}, non-finite {r.nonfinite}{what}",
+                  file=out)
 
 
 def _ein(t: reader.NdppTable, sec: str, iE: int) -> float:
@@ -367,7 +378,17 @@ def main(argv=None) -> int:
     ap.add_argument("--rel-tol", type=float, default=None,
                     help="with --certified: width of a settled enclosure relative to sum (l + 1/2)|a_l| "
                          "(default 1e-10)")
+    ap.add_argument("--repair-report", action="store_true",
+                    help="with --certified: add to each section what a repair of its negative rows would do "
+                         "(python -m ndpp_amd.run --repair-positivity); writes nothing")
     a = ap.parse_args(argv)
+    if a.repair_report and not a.certified:
+        print("validate: --repair-report needs --certified", file=sys.stderr)
+        return 2
+    if a.repair_report and a.moments is not None:
+        print("validate: --repair-report describes the repair of the stored rows, all moments: it does not go "
+              "together with --moments", file=sys.stderr)
+        return 2
     if a.certified and a.mu_points is not None:
         print("validate: --certified examines the whole interval; it does not go together with --mu-points",
               file=sys.stderr)
@@ -392,21 +413,27 @@ def main(argv=None) -> int:
     full, bad = {}, []
     for attrs, t in tables:
         name = attrs.get("name", t.name)
+        repair_rep = None
         try:
             if t.scatt_type == reader.SCATT_TYPE_TABULAR:
                 rep = tab_positivity(t)
             elif a.certified:
                 rep = minimum(t, n_moments=a.moments, rel_tol=rel_tol)
+                if a.repair_report:
+                    from . import repair
+                    _, repair_rep = repair.repair_sections(t, rel_tol=rel_tol)
             else:
                 rep = positivity(t, mu_points=a.mu_points, n_moments=a.moments)
         except lib.NdppError as e:
             print(f"validate: {name}: {e}", file=sys.stderr)
             return 2
         if isinstance(rep, MinimumReport):
-            _print_minimum(name, t, rep, sys.stdout)
+            _print_minimum(name, t, rep, sys.stdout, repair_rep)
         else:
             _print_report(name, t, rep, sys.stdout)
         full[name] = dict(rep.as_dict(), path=attrs.get("path"))
+        if repair_rep is not None:
+            full[name]["repair"] = repair_rep.as_dict()
         if not rep.positive:
             bad.append(name)
     print(f"{len(tables)} tables, {len(bad)} with negative" + (" or non-finite" if a.certified else "") + " rows"
