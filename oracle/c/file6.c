@@ -170,13 +170,60 @@ static double kahan_sum(const double *x, int n, int stride) {
   return s;
 }
 
+/* ---- the per-panel functional -------------------------------------------------------------
+ * The three integrators below are linear in one functional of a linear panel
+ * (xlo, xhi, flo, fhi) -> n values.  For the Legendre entries it is
+ * oracle_calc_int_pn_tablelin (n = the order); for the tabular entries it is
+ * tab_panel_bins (n = the number of lab-cosine bins).  It is passed down, never read from a
+ * global: the batch loops are OpenMP regions.  `tab` only selects the normalisation: the
+ * Legendre code divides by element 0 of each group (its P0), the tabular output by each
+ * group's sum over its bins. */
+typedef void (*panel_fn)(int n, double xlo, double xhi, double flo, double fhi, double *out);
+
+/* The integral of the linear panel over each of n equal bins of [-1, 1]: for EVERY bin k the
+ * panel is clipped to [b_k, b_{k+1}], b_k = -1 + 2k/n in long double, and the linear f is
+ * integrated over the intersection in long double.  The first and the last bin absorb what
+ * lies outside [-1, 1].  No walk along the panel, no bin search, no running accumulator:
+ * deliberately unlike the product's tab_spread.  legendre.F90:44's rule is kept: a panel
+ * narrower than FP_PRECISION contributes nothing. */
+static void tab_panel_bins(int n, double xlo, double xhi, double flo, double fhi, double *out) {
+  for (int k = 0; k < n; k++) out[k] = 0.0;
+  if (xhi - xlo < 1e-14) return;
+  const long double xl = xlo, xh = xhi, fl = flo, fh = fhi;
+  const long double s = (fh - fl) / (xh - xl);
+  for (int k = 0; k < n; k++) {
+    long double a = xl, b = xh;
+    if (k > 0) {
+      const long double bk = -1.0L + (2.0L * (long double)k) / (long double)n;
+      if (a < bk) a = bk;
+    }
+    if (k < n - 1) {
+      const long double bk1 = -1.0L + (2.0L * (long double)(k + 1)) / (long double)n;
+      if (b > bk1) b = bk1;
+    }
+    if (b > a) {
+      const long double fa = fl + s * (a - xl), fb = fl + s * (b - xl);
+      out[k] = (double)(0.5L * (b - a) * (fa + fb));
+    }
+  }
+}
+
+/* a group's P0: element 0 (Legendre), or the sum of its bins (tabular) */
+static double group_p0(const double *dg, int n, int tab) {
+  if (!tab) return dg[0];
+  long double s = 0.0L;
+  for (int k = 0; k < n; k++) s += dg[k];
+  return (double)s;
+}
+
 /* integrate_file6_cm_leg, scattdata_header.F90:1085-1266.  fEmu [np][M];
  * distro [G][L] pre-zeroed by the caller (:529). */
-void oracle_integrate_file6_cm_leg(const oracle_params *p, const double *fEmu, int np,
-                                   const double *mu, double Ein, double awr,
-                                   const double *Eout, int INTT, const double *thispdf,
-                                   const double *E_bins, int nbins, double *distro) {
-  const int L = p->order, M = p->mu_bins, NEG = p->ne_per_grp;
+static void file6_cm_impl(const oracle_params *p, const double *fEmu, int np,
+                          const double *mu, double Ein, double awr,
+                          const double *Eout, int INTT, const double *thispdf,
+                          const double *E_bins, int nbins, double *distro, int L, panel_fn panel,
+                          int tab) {
+  const int M = p->mu_bins, NEG = p->ne_per_grp;
   double deltamu = mu[1] - mu[0];
   double *pdf = (double *)malloc(sizeof(double) * (size_t)np);
   memcpy(pdf, thispdf, sizeof(double) * (size_t)np);
@@ -260,7 +307,7 @@ void oracle_integrate_file6_cm_leg(const oracle_params *p, const double *fEmu, i
         fmu[imu - 1] = proby * J * pEo;
       }
       for (int imu = 1; imu <= M - 1; imu++) {
-        oracle_calc_int_pn_tablelin(L, mu_l[imu - 1], mu_l[imu], fmu[imu - 1], fmu[imu], tmp);
+        panel(L, mu_l[imu - 1], mu_l[imu], fmu[imu - 1], fmu[imu], tmp);
         for (int l = 0; l < L; l++) fEl[l] = fEl[l] + tmp[l];
       }
       if ((iE != 1) && (iE != NEG))
@@ -272,7 +319,7 @@ void oracle_integrate_file6_cm_leg(const oracle_params *p, const double *fEmu, i
   }
   {
     double fEo = 0.0;
-    for (int g = g_lo; g <= g_hi; g++) fEo = fEo + distro[(size_t)(g - 1) * L];
+    for (int g = g_lo; g <= g_hi; g++) fEo = fEo + group_p0(distro + (size_t)(g - 1) * L, L, tab);
     if (fEo > 0.0) fEo = 1.0 / fEo;
     for (int g = g_lo; g <= g_hi; g++)
       for (int l = 0; l < L; l++) distro[(size_t)(g - 1) * L + l] *= fEo;
@@ -282,13 +329,21 @@ done:
   free(fEl);
 }
 
+void oracle_integrate_file6_cm_leg(const oracle_params *p, const double *fEmu, int np,
+                                   const double *mu, double Ein, double awr,
+                                   const double *Eout, int INTT, const double *thispdf,
+                                   const double *E_bins, int nbins, double *distro) {
+  file6_cm_impl(p, fEmu, np, mu, Ein, awr, Eout, INTT, thispdf, E_bins, nbins, distro, p->order,
+                oracle_calc_int_pn_tablelin, 0);
+}
+
 /* integrate_file6_lab_leg, scattdata_header.F90:1334-1450 */
-void oracle_integrate_file6_lab_leg(const oracle_params *p, const double *fEmu, int np,
-                                    const double *mu, const double *Eout, int INTT,
-                                    const double *thispdf, const double *E_bins, int nbins,
-                                    double *distro) {
+static void file6_lab_impl(const oracle_params *p, const double *fEmu, int np,
+                           const double *mu, const double *Eout, int INTT,
+                           const double *thispdf, const double *E_bins, int nbins,
+                           double *distro, int L, panel_fn panel, int tab) {
   (void)INTT;
-  const int L = p->order, M = p->mu_bins, G = nbins - 1;
+  const int M = p->mu_bins, G = nbins - 1;
   double *pdf = (double *)malloc(sizeof(double) * (size_t)(np + M + L));
   double *fint = pdf + np, *tmp = fint + M;
   memcpy(pdf, thispdf, sizeof(double) * (size_t)np);
@@ -328,7 +383,7 @@ void oracle_integrate_file6_lab_leg(const oracle_params *p, const double *fEmu, 
         for (int k = 0; k < M; k++) fint[k] = fint[k] + pdf[iE - 1] * col[k];
       }
       for (int imu = 1; imu <= M - 1; imu++) {
-        oracle_calc_int_pn_tablelin(L, mu[imu - 1], mu[imu], fint[imu - 1], fint[imu], tmp);
+        panel(L, mu[imu - 1], mu[imu], fint[imu - 1], fint[imu], tmp);
         for (int l = 0; l < L; l++) dg[l] = dg[l] + tmp[l];
       }
     }
@@ -337,7 +392,7 @@ void oracle_integrate_file6_lab_leg(const oracle_params *p, const double *fEmu, 
       double *dg = distro + (size_t)g * L;
       if ((Eout[0] > E_bins[g]) && (Eout[0] <= E_bins[g + 1])) {
         for (int imu = 1; imu <= M - 1; imu++) {
-          oracle_calc_int_pn_tablelin(L, mu[imu - 1], mu[imu], fEmu[imu - 1], fEmu[imu], tmp);
+          panel(L, mu[imu - 1], mu[imu], fEmu[imu - 1], fEmu[imu], tmp);
           for (int l = 0; l < L; l++) dg[l] = dg[l] + tmp[l];
         }
       } else {
@@ -345,17 +400,33 @@ void oracle_integrate_file6_lab_leg(const oracle_params *p, const double *fEmu, 
       }
     }
   }
-  double f_lo = 1.0 / kahan_sum(distro, G, L); /* ONE / sum(distro(1,:)), :1447 */
+  double f_lo;
+  if (!tab) {
+    f_lo = 1.0 / kahan_sum(distro, G, L); /* ONE / sum(distro(1,:)), :1447 */
+  } else { /* the same sum over the groups, each group's P0 the sum of its bins */
+    double *p0 = (double *)malloc(sizeof(double) * (size_t)G);
+    for (int g = 0; g < G; g++) p0[g] = group_p0(distro + (size_t)g * L, L, 1);
+    f_lo = 1.0 / kahan_sum(p0, G, 1);
+    free(p0);
+  }
   for (int k = 0; k < G * L; k++) distro[k] = distro[k] * f_lo;
   free(pdf);
 }
 
+void oracle_integrate_file6_lab_leg(const oracle_params *p, const double *fEmu, int np,
+                                    const double *mu, const double *Eout, int INTT,
+                                    const double *thispdf, const double *E_bins, int nbins,
+                                    double *distro) {
+  file6_lab_impl(p, fEmu, np, mu, Eout, INTT, thispdf, E_bins, nbins, distro, p->order,
+                 oracle_calc_int_pn_tablelin, 0);
+}
+
 /* law9_scatter_lab_leg, scattdata_header.F90:1274-1326; edata = edist%data */
-void oracle_law9_scatter_lab_leg(const oracle_params *p, const double *fmu,
-                                 const double *edata, double Ein, const double *E_bins,
-                                 int nbins, const double *mu, double *distro) {
-  const int L = p->order, M = p->mu_bins;
-  double tmp[16];
+static void law9_impl(const oracle_params *p, const double *fmu, const double *edata,
+                      double Ein, const double *E_bins, int nbins, const double *mu,
+                      double *distro, int L, panel_fn panel) {
+  const int M = p->mu_bins;
+  double tmp[128]; /* 11 orders, or up to 128 bins */
   int NR = (int)edata[0];
   int NE = (int)edata[1 + 2 * NR];
   double T = oracle_interpolate_tab1(edata, Ein);
@@ -372,10 +443,16 @@ void oracle_law9_scatter_lab_leg(const oracle_params *p, const double *fmu,
     double pE = (exp(-Egp1 / T) * (T + Egp1)) - (exp(-Eg / T) * (T + Eg));
     pE = -T * pE / I;
     for (int imu = 1; imu <= M - 1; imu++) {
-      oracle_calc_int_pn_tablelin(L, mu[imu - 1], mu[imu], fmu[imu - 1], fmu[imu], tmp);
+      panel(L, mu[imu - 1], mu[imu], fmu[imu - 1], fmu[imu], tmp);
       for (int l = 0; l < L; l++) dg[l] = dg[l] + tmp[l] * pE;
     }
   }
+}
+
+void oracle_law9_scatter_lab_leg(const oracle_params *p, const double *fmu,
+                                 const double *edata, double Ein, const double *E_bins,
+                                 int nbins, const double *mu, double *distro) {
+  law9_impl(p, fmu, edata, Ein, E_bins, nbins, mu, distro, p->order, oracle_calc_int_pn_tablelin);
 }
 
 /* The edist branches of integrate_distro (scattdata_header.F90:593-656) for
@@ -385,12 +462,13 @@ void oracle_law9_scatter_lab_leg(const oracle_params *p, const double *fmu,
  * frame_cm = 1: unitbase + integrate_file6_cm_leg; 0: unitbase +
  * integrate_file6_lab_leg.  row_lo[i] = iE-1 of scatt_interp_distro.
  * out [n_ein][G][L].  Returns 0, or -1 if a search left its table. */
-int oracle_file6_leg_batch(const oracle_params *p, double awr, int frame_cm, int n_ein,
-                           const double *ein, const int *row_lo, int n_rows,
-                           const double *e_grid, const int *row_ptr, const double *eout,
-                           const double *pdf, const int *intt, const double *f, int G,
-                           const double *e_bins, double *out, int nthreads) {
-  const int L = p->order, M = p->mu_bins;
+static int file6_batch_impl(const oracle_params *p, double awr, int frame_cm, int n_ein,
+                            const double *ein, const int *row_lo, int n_rows,
+                            const double *e_grid, const int *row_ptr, const double *eout,
+                            const double *pdf, const int *intt, const double *f, int G,
+                            const double *e_bins, double *out, int nthreads, int L,
+                            panel_fn panel, int tab) {
+  const int M = p->mu_bins;
   if (nthreads <= 0) nthreads = omp_get_max_threads();
   double *gmu = (double *)malloc(sizeof(double) * (size_t)M);
   oracle_mu_grid(M, gmu);
@@ -411,40 +489,78 @@ int oracle_file6_leg_batch(const oracle_params *p, double awr, int frame_cm, int
     memset(o, 0, sizeof(double) * (size_t)G * L);
     if (nub < 0) bad |= 1;
     else if (frame_cm)
-      oracle_integrate_file6_cm_leg(p, fE, nub, gmu, ein[i], awr, Eo, INTT, pd, e_bins, G + 1, o);
+      file6_cm_impl(p, fE, nub, gmu, ein[i], awr, Eo, INTT, pd, e_bins, G + 1, o, L, panel, tab);
     else
-      oracle_integrate_file6_lab_leg(p, fE, nub, gmu, Eo, INTT, pd, e_bins, G + 1, o);
+      file6_lab_impl(p, fE, nub, gmu, Eo, INTT, pd, e_bins, G + 1, o, L, panel, tab);
     free(Eo);
   }
   free(gmu);
   return bad ? -1 : 0;
 }
 
+int oracle_file6_leg_batch(const oracle_params *p, double awr, int frame_cm, int n_ein,
+                           const double *ein, const int *row_lo, int n_rows,
+                           const double *e_grid, const int *row_ptr, const double *eout,
+                           const double *pdf, const int *intt, const double *f, int G,
+                           const double *e_bins, double *out, int nthreads) {
+  return file6_batch_impl(p, awr, frame_cm, n_ein, ein, row_lo, n_rows, e_grid, row_ptr, eout, pdf,
+                          intt, f, G, e_bins, out, nthreads, p->order, oracle_calc_int_pn_tablelin, 0);
+}
+
+/* The tabular output: the same integrators with the per-panel functional replaced by the
+ * integral over each of n_tab equal lab-cosine bins.  out [n_ein][G][n_tab]. */
+int oracle_file6_tab_batch(const oracle_params *p, double awr, int frame_cm, int n_ein,
+                           const double *ein, const int *row_lo, int n_rows,
+                           const double *e_grid, const int *row_ptr, const double *eout,
+                           const double *pdf, const int *intt, const double *f, int G,
+                           const double *e_bins, double *out, int nthreads, int n_tab) {
+  if (n_tab < 1 || n_tab > 128) return -2;
+  return file6_batch_impl(p, awr, frame_cm, n_ein, ein, row_lo, n_rows, e_grid, row_ptr, eout, pdf,
+                          intt, f, G, e_bins, out, nthreads, n_tab, tab_panel_bins, 1);
+}
+
 /* law 9 with adist rows: integrate_distro :605-638 -- both rows + blend */
-int oracle_law9_leg_batch(const oracle_params *p, int n_ein, const double *ein,
-                          const int *row_lo, const double *w_hi, int n_rows,
-                          const double *f_tab, const double *edata, int G,
-                          const double *e_bins, double *out, int nthreads) {
-  const int L = p->order, M = p->mu_bins;
+static int law9_batch_impl(const oracle_params *p, int n_ein, const double *ein,
+                           const int *row_lo, const double *w_hi, int n_rows,
+                           const double *f_tab, const double *edata, int G,
+                           const double *e_bins, double *out, int nthreads, int L,
+                           panel_fn panel) {
+  const int M = p->mu_bins;
   if (nthreads <= 0) nthreads = omp_get_max_threads();
   double *gmu = (double *)malloc(sizeof(double) * (size_t)M);
   oracle_mu_grid(M, gmu);
 #pragma omp parallel for schedule(dynamic, 1) num_threads(nthreads)
   for (int i = 0; i < n_ein; i++) {
-    double lo[16 * 128], hi[16 * 128];
+    double *lo = (double *)calloc((size_t)2 * G * L, sizeof(double)), *hi = lo + (size_t)G * L;
     (void)n_rows;
-    memset(lo, 0, sizeof(double) * (size_t)G * L);
-    memset(hi, 0, sizeof(double) * (size_t)G * L);
     const double *f0 = f_tab + (size_t)row_lo[i] * M;
-    oracle_law9_scatter_lab_leg(p, f0, edata, ein[i], e_bins, G + 1, gmu, lo);
-    oracle_law9_scatter_lab_leg(p, f0 + M, edata, ein[i], e_bins, G + 1, gmu, hi);
+    law9_impl(p, f0, edata, ein[i], e_bins, G + 1, gmu, lo, L, panel);
+    law9_impl(p, f0 + M, edata, ein[i], e_bins, G + 1, gmu, hi, L, panel);
     double f = w_hi[i];
     double *o = out + (size_t)i * G * L;
     for (int k = 0; k < G * L; k++) {
       double r = (1.0 - f) * lo[k];
       o[k] = r + f * hi[k];
     }
+    free(lo);
   }
   free(gmu);
   return 0;
+}
+
+int oracle_law9_leg_batch(const oracle_params *p, int n_ein, const double *ein,
+                          const int *row_lo, const double *w_hi, int n_rows,
+                          const double *f_tab, const double *edata, int G,
+                          const double *e_bins, double *out, int nthreads) {
+  return law9_batch_impl(p, n_ein, ein, row_lo, w_hi, n_rows, f_tab, edata, G, e_bins, out, nthreads,
+                         p->order, oracle_calc_int_pn_tablelin);
+}
+
+int oracle_law9_tab_batch(const oracle_params *p, int n_ein, const double *ein,
+                          const int *row_lo, const double *w_hi, int n_rows,
+                          const double *f_tab, const double *edata, int G,
+                          const double *e_bins, double *out, int nthreads, int n_tab) {
+  if (n_tab < 1 || n_tab > 128) return -2;
+  return law9_batch_impl(p, n_ein, ein, row_lo, w_hi, n_rows, f_tab, edata, G, e_bins, out, nthreads,
+                         n_tab, tab_panel_bins);
 }

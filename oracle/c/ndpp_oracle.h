@@ -134,6 +134,20 @@ int    oracle_law9_leg_batch(const oracle_params *p, int n_ein, const double *ei
                              const int *row_lo, const double *w_hi, int n_rows,
                              const double *f_tab, const double *edata, int G,
                              const double *e_bins, double *out, int nthreads);
+/* The tabular output (no Fortran behind it): the integrators above with the per-panel
+ * functional replaced by the integral of the linear panel over each of n_tab equal bins of
+ * the lab cosine, clipped bin by bin in long double.  out [n_ein][G][n_tab]; normalised by
+ * the sum over groups and bins (CM) / over the groups' bin sums (lab).  -2: n_tab outside
+ * 1..128. */
+int    oracle_file6_tab_batch(const oracle_params *p, double awr, int frame_cm, int n_ein,
+                              const double *ein, const int *row_lo, int n_rows,
+                              const double *e_grid, const int *row_ptr, const double *eout,
+                              const double *pdf, const int *intt, const double *f, int G,
+                              const double *e_bins, double *out, int nthreads, int n_tab);
+int    oracle_law9_tab_batch(const oracle_params *p, int n_ein, const double *ein,
+                             const int *row_lo, const double *w_hi, int n_rows,
+                             const double *f_tab, const double *edata, int G,
+                             const double *e_bins, double *out, int nthreads, int n_tab);
 
 /* ---- thermal S(alpha,beta) tables (oracle/c/sab.c) ----
  * Flattened SAlphaBeta (ace_header.F90:201-235); identical layout to

@@ -5,7 +5,10 @@ import numpy as np
 import pytest
 
 from conftest import load_golden
-from synth import kalbach_rows, law9_edata, mu_grid, nuclide_case
+from synth import kalbach_rows, mu_grid, nuclide_case
+from tabular_ref import (BIN_TOL, F4_LEVEL_R, FILE6_TOL, GROUPS, bin_err, bind_tab, centres, edges,
+                         enclosure_violation, file4_level_case, file4_numpy, file6_case, law9_case, law9_numpy,
+                         oracle_file6, oracle_law9)
 
 pytestmark = pytest.mark.gpu
 
@@ -29,10 +32,6 @@ def refine_err(tab_n, tab_2n):
     return (np.abs(pair - tab_n).max(axis=(1, 2)) / scale).max()
 
 
-def centres(n):
-    return -1.0 + (2.0 * np.arange(n) + 1.0) / n
-
-
 # ---- file 4 ----------------------------------------------------------------------------------
 def file4_case(A, n_ein=24, seed=5):
     rng = np.random.default_rng(seed)
@@ -46,52 +45,6 @@ def file4_case(A, n_ein=24, seed=5):
     w = (ein - e_grid[row]) / (e_grid[row + 1] - e_grid[row])
     bins = np.array([0.0, 1e-3, 0.05, 0.5, 2.0, 20.0])
     return dict(A=A, f_tab=f_tab, ein=ein, row=row.astype(np.int32), w=w, bins=bins)
-
-
-def f4_lab(R, w):
-    if R == 1.0:
-        return np.sqrt(0.5 * (1.0 + w))
-    return (1.0 + R * w) / np.sqrt(1.0 + R * R + 2.0 * R * w)
-
-
-def file4_numpy(c, N):
-    """Independent restatement: the piecewise-linear f(w) of the trapezoid rule, cut at the grid
-    points, at w = -R and at the CM cosines of every bin edge (roots of the kinematics' quadratic),
-    each piece integrated exactly and given to the bin of its midpoint."""
-    A, M = c["A"], c["f_tab"].shape[1]
-    dmu = 2.0 / (M - 1)
-    wg = -1.0 + np.arange(M) * dmu
-    wg[-1] = 1.0
-    edges = -1.0 + 2.0 * np.arange(N + 1) / N
-    out = np.zeros((len(c["ein"]), len(c["bins"]) - 1, N))
-    for i, (E, r, fb) in enumerate(zip(c["ein"], c["row"], c["w"])):
-        f = (1.0 - fb) * c["f_tab"][r] + fb * c["f_tab"][r + 1]
-        R = A
-        for g in range(len(c["bins"]) - 1):
-            wl = ((c["bins"][g] * (1 + A) ** 2 - E * (1 + R * R)) / (2 * R * E)).clip(-1, 1)
-            wh = ((c["bins"][g + 1] * (1 + A) ** 2 - E * (1 + R * R)) / (2 * R * E)).clip(-1, 1)
-            if wl == wh and abs(wl) == 1.0:
-                continue
-            pts = [wl, wh] + list(wg[(wg > wl) & (wg < wh)])
-            if R < 1.0 and wl < -R < wh:
-                pts.append(-R)
-            # s = sqrt(1 + R^2 + 2 R w) solves s^2 - 2 mu s + (1 - R^2) = 0
-            for mu_e in edges:
-                disc = mu_e * mu_e - 1.0 + R * R
-                if disc < 0:
-                    continue
-                for s in (mu_e + np.sqrt(disc), mu_e - np.sqrt(disc)):
-                    if s > 0:
-                        we = (s * s - 1.0 - R * R) / (2.0 * R)
-                        if wl < we < wh:
-                            pts.append(we)
-            pts = np.unique(pts)
-            a, b = pts[:-1], pts[1:]
-            fa, fbv = np.interp(a, wg, f), np.interp(b, wg, f)
-            mass = 0.5 * (b - a) * (fa + fbv)
-            k = np.clip(np.floor((f4_lab(R, 0.5 * (a + b)) + 1.0) * 0.5 * N).astype(int), 0, N - 1)
-            np.add.at(out[i, g], k, mass)
-    return out
 
 
 @pytest.mark.parametrize("A", [0.99917, 1.0, 12.0, 236.0058])
@@ -117,11 +70,12 @@ def test_file4_sum_rule_refinement_frame(hip, A):
         p1 = (t * centres(128)).sum(axis=2)
         assert (np.abs(p1 - leg[:, :, 1]) <= leg[:, :, 0] / 128 + 1e-15).all()
     # independent restatement
-    ref = file4_numpy(c, 32)
-    scale = np.abs(leg[:, :, 0]).max(axis=1)[:, None, None]
-    err = (np.abs(tabs[32] - ref) / scale).max()
-    print(f"file4 A={A}: numpy restatement {err:.2e}")
-    assert err <= 1e-12
+    for N in (7, 32, 128):
+        ref, _ = file4_numpy(c, N)
+        scale = np.abs(leg[:, :, 0]).max(axis=1)[:, None, None]
+        err = (np.abs(tabs[N] - ref) / scale).max()
+        print(f"file4 A={A} N={N}: numpy restatement {err:.2e}")
+        assert err <= 1e-12
     # repeatability
     again, _ = hip.elastic_tab_batch(p, 32, *args)
     assert np.array_equal(again, tabs[32])
@@ -180,22 +134,160 @@ def test_law9_sum_rule_and_restatement(hip):
     assert (np.abs((t * centres(128)).sum(axis=2) - leg[:, :, 1]) <= np.abs(leg[:, :, 0]) / 128 + 1e-15).all()
     # numpy: the blended row's exact bin integrals, scaled by each group's P0 (law 9's energy
     # factor is common to both rows)
-    mu = mu_grid(M)
     for N in (7, 32):
-        edges = -1.0 + 2.0 * np.arange(N + 1) / N
-        x = np.unique(np.concatenate([mu, edges]))
-        for i, (r, w) in enumerate(zip(g["l9_row"], g["l9_w"])):
-            f = (1 - w) * g["l9_f_tab"][r] + w * g["l9_f_tab"][r + 1]
-            fx = np.interp(x, mu, f)
-            mass = 0.5 * np.diff(x) * (fx[1:] + fx[:-1])
-            k = np.clip(np.floor((0.5 * (x[1:] + x[:-1]) + 1) * 0.5 * N).astype(int), 0, N - 1)
-            frac = np.bincount(k, weights=mass, minlength=N)
-            frac = frac / frac.sum()
-            want = leg[i, :, 0][:, None] * frac[None, :]
+        want = law9_numpy(g["l9_f_tab"], g["l9_row"], g["l9_w"], leg[:, :, 0], N)
+        for i in range(len(want)):
             scale = max(np.abs(leg[i, :, 0]).max(), 1e-300)
-            assert np.abs(tabs[N][i] - want).max() / scale <= 1e-12
+            assert np.abs(tabs[N][i] - want[i]).max() / scale <= 1e-12
     again, _ = hip.law9_tab_batch(p, 32, *args)
     assert np.array_equal(again, tabs[32])
+
+
+# ---- every bin against a restatement -----------------------------------------------------------
+# The sum rule and the refinement property cannot see mass in the wrong bin, and the first moment
+# tolerates half a bin.  Below, every bin of file 6 and law 9 is compared with the oracle's tabular
+# entries (oracle/c/file6.c: the Legendre integrators pinned to the Fortran, with the per-panel
+# functional replaced by a long double integral clipped to each bin), and every bin of file 4 with the
+# numpy restatement, at small mu grids too -- where one panel spans many bins.  The bar is BIN_TOL =
+# 1e-12 of the E_in's largest group P0 throughout.
+NB = (1, 3, 7, 128)
+F6_AWRS = (0.9992, 2.0, 236.0058)
+
+
+def file6_args(T, ein, row, bins):
+    return (ein, row, T["e_grid"], T["row_ptr"], T["eout"], T["pdf"], T["intt"], T["f"], bins)
+
+
+@pytest.mark.parametrize("frame", [1, 0], ids=["cm", "lab"])
+@pytest.mark.parametrize("M", [2, 5, 33, 513])
+def test_file6_every_bin_vs_oracle(hip, oracle, M, frame):
+    bind_tab(oracle)
+    worst, where = 0.0, None
+    for intt in (1, 2):
+        T, ein, row = file6_case(M, intt)
+        for awr in F6_AWRS:
+            for G, bins in GROUPS.items():
+                for neg in (2, 10):
+                    p = hip.Params.default(6, M)
+                    p.ne_per_grp = neg
+                    for N in NB:
+                        tab, st = hip.file6_tab_batch(p, N, awr, frame, *file6_args(T, ein, row, bins))
+                        ref = oracle_file6(oracle, T, awr, frame, ein, row, bins, n_tab=N, neg=neg)
+                        assert (st == 0).all() and np.isfinite(ref).all()
+                        assert np.array_equal((tab != 0).any(axis=2), (ref != 0).any(axis=2)), (intt, awr, G, neg, N)
+                        err, at = bin_err(tab, ref, ref.sum(axis=2))
+                        if err > worst:
+                            worst, where = err, dict(M=M, N=N, frame="cm" if frame else "lab", intt=intt, awr=awr, G=G,
+                                                     ne_per_grp=neg, ein_group_bin=at)
+    print(f"file 6 {'cm' if frame else 'lab'} M={M}: worst bin vs oracle {worst:.2e} at {where}")
+    assert worst <= BIN_TOL, where
+
+
+@pytest.mark.parametrize("frame", [1, 0], ids=["cm", "lab"])
+@pytest.mark.parametrize("M", [2, 5, 33, 513])
+def test_file6_bins_enclose_the_legendre_moments(hip, M, frame):
+    """T >= 0, and sum_k T_k min_bin P_l <= a_l <= sum_k T_k max_bin P_l for l = 1..5 against the
+    GPU's own Legendre moments on the same inputs -- moments that are pinned to the Fortran."""
+    worst = 0.0
+    for intt in (1, 2):
+        T, ein, row = file6_case(M, intt)
+        for awr in F6_AWRS:
+            for bins in GROUPS.values():
+                p = hip.Params.default(6, M)
+                leg, _ = hip.file6_leg_batch(p, awr, frame, *file6_args(T, ein, row, bins))
+                for N in (32, 128):
+                    tab, st = hip.file6_tab_batch(p, N, awr, frame, *file6_args(T, ein, row, bins))
+                    assert (st == 0).all() and (tab >= 0).all()
+                    worst = max(worst, enclosure_violation(tab, leg))
+    print(f"file 6 {'cm' if frame else 'lab'} M={M}: enclosure violation {worst:.2e}")
+    assert worst <= FILE6_TOL
+
+
+def test_file6_nonfinite_rows_are_the_oracles(hip, oracle):
+    """Where the reference's integrators give non-finite rows, the tabular rows that are non-finite
+    are those of the oracle's bins, and exactly those E_in carry NDPP_ST_NONFINITE (a row-level
+    pattern, not an element-wise one).  A log-linear (intt = 4) CM table with its first E_out at 1e-5,
+    prepared as test_file6_vs_oracle_bigger does, stays finite throughout; in the second table the rows
+    1 and 3 interpolate logarithmically in E_out (intt 5 and 3) and are evaluated at the unit-base
+    origin (log 0): every E_in whose lower bracketing row is one of them is non-finite, the others
+    are not."""
+    bind_tab(oracle)
+    M = 2001
+    p = hip.Params.default(6, M)
+    for schemes, frames in (((4, 4, 4, 4, 4), (1,)), ((4, 5, 4, 3, 4), (1, 0))):
+        T = kalbach_rows(M, 5, 20, 40, 0.1, 20.0, seed=242, dup_last=False, intt=4)
+        T["intt"][:] = schemes
+        T["eout"][T["row_ptr"][:-1]] = 1e-5
+        rng = np.random.default_rng(7)
+        ein = np.sort(rng.uniform(T["e_grid"][0], T["e_grid"][-1], 6))
+        row = (np.searchsorted(T["e_grid"], ein, side="right") - 1).clip(0, 3).astype(np.int32)
+        for frame in frames:
+            for bins in (np.array([0.0, 6.25e-7, 20.0]), GROUPS[12]):
+                for N in (7, 32):
+                    tab, st = hip.file6_tab_batch(p, N, 236.0058, frame, *file6_args(T, ein, row, bins))
+                    ref = oracle_file6(oracle, T, 236.0058, frame, ein, row, bins, n_tab=N)
+                    bad_ref = ~np.isfinite(ref).all(axis=(1, 2))
+                    bad = ~np.isfinite(tab).all(axis=(1, 2))
+                    print(f"file 6 {'cm' if frame else 'lab'} intt={schemes} G={len(bins) - 1} N={N}: non-finite rows "
+                          f"oracle {bad_ref.astype(int)}, library {bad.astype(int)}, status {st}")
+                    assert np.array_equal(bad, bad_ref)
+                    assert np.array_equal((st & 1) != 0, bad_ref)             # NDPP_ST_NONFINITE = 1
+                    if len(set(schemes)) > 1:
+                        assert bad_ref.any() and not bad_ref.all()
+
+
+@pytest.mark.parametrize("M", [2, 5, 33])
+def test_law9_every_bin_vs_oracle_and_numpy(hip, oracle, M):
+    bind_tab(oracle)
+    c = law9_case(M)
+    args = (c["ein"], c["row"], c["w"], c["f_tab"], c["edata"], c["bins"])
+    p = hip.Params.default(6, M)
+    oleg = oracle_law9(oracle, c)
+    leg, _ = hip.law9_leg_batch(p, *args)
+    for N in NB + (32,):
+        tab, st = hip.law9_tab_batch(p, N, *args)
+        assert (st == 0).all() and (tab >= 0).all()
+        assert (tab[0] == 0).all()                                   # E_in below U
+        if N in NB:
+            ref = oracle_law9(oracle, c, n_tab=N)
+            assert np.array_equal((tab != 0).any(axis=2), (ref != 0).any(axis=2))
+            e1, at1 = bin_err(tab, ref, oleg[:, :, 0])
+            e2, at2 = bin_err(tab, law9_numpy(c["f_tab"], c["row"], c["w"], oleg[:, :, 0], N), oleg[:, :, 0])
+            print(f"law 9 M={M} N={N}: worst bin vs oracle {e1:.2e} at {at1}, vs numpy {e2:.2e} at {at2}")
+            assert e1 <= BIN_TOL and e2 <= BIN_TOL, (M, N, at1, at2)
+        if N in (32, 128):
+            v = enclosure_violation(tab, leg)
+            print(f"law 9 M={M} N={N}: enclosure violation {v:.2e}")
+            assert v <= FILE6_TOL
+    assert (oleg[1, -3:] == 0).all() and (tab[1, -3:] == 0).all()    # groups above E_in - U
+
+
+@pytest.mark.parametrize("M", [5, 33, 2001])
+def test_file4_level_every_bin_vs_numpy(hip, M):
+    """An inelastic level (Q = -0.0449, A = 236.0058) from R = 0.05 to R = 20: both branches of the
+    lab cosine's inverse, the descending bin walk below w = -R, the split at w = -R, groups narrower
+    than a w panel."""
+    c = file4_level_case(M)
+    p = hip.Params.default(4, M)
+    args = (c["A"], 2.53e-8, 0.0, c["Q"], c["ein"], c["row"], c["w"], c["f_tab"], c["bins"])
+    leg, stl = hip.elastic_leg_batch(p, *args)
+    assert (stl == 0).all()
+    for N in (1, 3, 7, 32, 128):
+        tab, st = hip.elastic_tab_batch(p, N, *args)
+        ref, p0 = file4_numpy(c, N, c["Q"])
+        assert (st == 0).all() and (tab >= 0).all()
+        err, at = bin_err(tab, ref, p0)
+        sr = sum_rule_err(tab, leg)
+        print(f"file 4 level M={M} N={N}: worst bin vs numpy {err:.2e} at (E_in, group, bin) {at} "
+              f"(R = {c['R'][at[0]]:.6g}); sum rule {sr:.2e}")
+        assert err <= BIN_TOL, (M, N, at)
+        assert sr <= 1e-13
+        # R < 1: no lab cosine below sqrt(1 - R^2) (- 1e-12: the rounding of the cosine at w = -R)
+        for i, R in enumerate(c["R"]):
+            if R < 1.0:
+                empty = edges(N)[1:] < np.sqrt(1.0 - R * R) - 1e-12
+                assert (tab[i][:, empty] == 0).all(), (M, N, i)
+    assert len(F4_LEVEL_R) == len(c["ein"])
 
 
 # ---- free gas --------------------------------------------------------------------------------
