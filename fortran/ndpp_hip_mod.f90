@@ -26,6 +26,7 @@ module ndpp_hip_mod
   private
   public :: ndpp_params, calc_elastic_grid_hip, calc_inelastic_grid_hip, ndpp_hip_error
   public :: calc_scattsab_hip, calc_chi_hip, convert_distro_hip, calc_scatt_hip
+  public :: ndpp_sab_flat, ndpp_sab_tab_batch     ! thermal tables in lab-cosine bins: the C entry itself
 
   ! == struct ndpp_params of include/ndpp_hip.h
   type, bind(C) :: ndpp_params
@@ -107,6 +108,23 @@ module ndpp_hip_mod
       real(c_double), intent(out) :: scatt_mat(*)     ! (order, groups, n_ein)
       integer(c_int) :: rc
     end function ndpp_sab_batch
+
+    ! int ndpp_sab_tab_batch(const ndpp_params*, const ndpp_sab_flat*, int n_tab, int n_ein,
+    !     const double* ein, int G, const double* e_bins, double* el, double* inel,
+    !     double* scatt_mat, int* status)
+    ! The tabular twin (interface only: calc_scattsab_hip keeps returning -22 for tabular).
+    function ndpp_sab_tab_batch(p, t, n_tab, n_ein, ein, G, e_bins, el, inel, scatt_mat, status) &
+        bind(C, name="ndpp_sab_tab_batch") result(rc)
+      import :: c_int, c_double, c_ptr, ndpp_params, ndpp_sab_flat
+      type(ndpp_params), intent(in) :: p              ! p % order is not read
+      type(ndpp_sab_flat), intent(in) :: t
+      integer(c_int), value :: n_tab, n_ein, G
+      real(c_double), intent(in) :: ein(*), e_bins(*)
+      type(c_ptr), value :: el, inel                  ! c_null_ptr: parts not wanted
+      real(c_double), intent(out) :: scatt_mat(*)     ! (n_tab, groups, n_ein)
+      type(c_ptr), value :: status                    ! int(n_ein) NDPP_ST_* bits, or c_null_ptr
+      integer(c_int) :: rc
+    end function ndpp_sab_tab_batch
 
     ! int ndpp_chi_batch(const ndpp_chi_nuclide*, int n_prompt, const ndpp_chi_spectrum*,
     !     int n_delay, const ndpp_chi_spectrum*, int G, const double* e_bins, int n_ein,

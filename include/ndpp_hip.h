@@ -336,6 +336,42 @@ int ndpp_sab_batch(const ndpp_params *p, const ndpp_sab_flat *t, int n_ein,
                    const double *ein, int G, const double *e_bins, double *el,
                    double *inel, double *scatt_mat);
 
+/* Tabular output of a thermal table (scatt_type = NDPP_SCATT_TABULAR), opt-in: the writer and the
+ * driver take it only where asked to (ndpp_nuclide_file is_sab = 2, `run --thermal-tabular`).
+ * A thermal table holds discrete cosines with weights: the density behind ndpp_sab_batch's
+ * a_l = sum_i w_i P_l(mu_i) is sum_i w_i delta(mu - mu_i), and its tabular form is exact -- every
+ * mass w_i goes, whole, into the bin that holds mu_i.  No quadrature, nothing has to settle.
+ *   Bins    n_tab = N equal bins of the lab cosine, 1 <= N <= NDPP_MAX_TAB_BINS (else
+ *           NDPP_EINVAL), edges -1 + 2k/N as for the other tabular paths.
+ *   Bin of a cosine   the value of ONE floating-point expression,
+ *             k = (int)floor((mu + 1.0) * (0.5 * N)), clamped to 0 .. N-1:
+ *           a cosine on an interior edge goes to the upper bin, mu = 1 to bin N-1, a cosine
+ *           slightly outside [-1, 1] to the end bin.  A cosine that is not finite goes into no bin
+ *           and sets NDPP_ST_NONFINITE in the status word of every E_in that read it.  The cosines
+ *           are computed exactly as the Legendre kernels compute them (the (1-f) mu_a + f mu_b
+ *           blends; the single Bragg-edge cosine 1 - E_bragg/E_in of the reference's coherent
+ *           branch, quirk included), in the same translation unit and arithmetic: bins and moments
+ *           describe the same set of masses.
+ *   Value   T[iE][g][k] is what the Legendre kernel accumulates for order 0 of (iE, g), restricted
+ *           to the masses whose cosine lies in bin k: the masses in the same order (io ascending,
+ *           imu ascending; continuous mode: lower edge term, upper edge term, interior points,
+ *           then / NMU), the same equal or skewed weights, sigma factors, E_in interpolation of the
+ *           continuous mode's per-table-row results, and NDPP_ST_RANGE cases.
+ *   Normalisation   combine_sab_grid with a group's bin sum in the place of its P0: s is the Kahan
+ *           sum of el + inel over (g, then k) in storage order; rows are scaled by 1/s when s > 0,
+ *           else zero; the last point copies its neighbour.
+ * At N = 1 the three outputs are ndpp_sab_batch's at order 1 (L = 1), bit for bit.  A bin has one
+ * fixed order of summation: two calls give the same bits.
+ * A histogram of point masses moves mass from one bin to the next as E_in moves, so these rows do
+ * not interpolate between grid points the way the piecewise-linear paths' rows do: hence opt-in.
+ *   el, inel, scatt_mat [n_ein][G][n_tab], bin index fastest; el and inel optional (NULL)
+ *   status [n_ein]      NDPP_ST_* bits, may be NULL
+ * The checks are ndpp_sab_batch's, with n_tab in the place of p->order (which is not read), and
+ * all come before the device is asked for.                                                   */
+int ndpp_sab_tab_batch(const ndpp_params *p, const ndpp_sab_flat *t, int n_tab,
+                       int n_ein, const double *ein, int G, const double *e_bins,
+                       double *el, double *inel, double *scatt_mat, int *status);
+
 /* ---- fission spectrum chi ---------------------------------------------------
  * One secondary energy distribution: a fission reaction's `edist` (one entry per
  * nested distribution, in `edist%next` chain order -- calc_chi, chi.F90:49-87) or
@@ -600,7 +636,10 @@ int  ndpp_finish_scatt(const ndpp_output_options *o, ndpp_scatt_result *r, int n
                        const double *e_bins, double *thin_report);
 /* The table's library file: header (init_library ndpp.F90:1246), scatter section
  * (print_scatt, group indices ndpp.F90:648-679), chi section when integrate_chi and
- * n_chi > 0 (print_chi); is_sab: thermal table (nuscatter flag written as 0).            */
+ * n_chi > 0 (print_chi); is_sab: 0 a neutron table; 1 a thermal table (nuscatter flag written
+ * as 0, no chi), refused with scatt_type tabular; 2 a thermal table whose matrix may be tabular
+ * (ndpp_sab_tab_batch): the header is the one is_sab = 1 writes, with scatt_type and scatt_order
+ * as the options give them.                                                               */
 long ndpp_nuclide_file(const ndpp_output_options *o, const char *name, int name_len, double kT,
                        int is_sab, const ndpp_scatt_result *r, int n_bins, const double *e_bins,
                        int n_chi, int n_prec, const double *e_chi, const double *chi_t,

@@ -18,7 +18,7 @@ from .lib import (_check, Params, Stats, NdppError, load, library_path, mu_grid,
                   Repair, scatt_repair, REPAIR_BEST, REPAIR_HEAT, REPAIR_UNIFORM, HOW_UNEXAMINED, HOW_UNTOUCHED,
                   HOW_HEAT, HOW_UNIFORM, HOW_UNREPAIRABLE, HOW_NONFINITE,
                   SCATT_LEGENDRE, SCATT_TABULAR, MAX_TAB_BINS, elastic_tab_batch, file6_tab_batch,
-                  law9_tab_batch, scatt_nuclide_tab, scatt_library_tab, scatt_library_at, grid_error,
+                  law9_tab_batch, sab_tab_batch, scatt_nuclide_tab, scatt_library_tab, scatt_library_at, grid_error,
                   thin_segments, thin_bounded, lib_compare)
 from .scatt import binary_search, elastic_brackets, calc_elastic_grid  # noqa: F401
 

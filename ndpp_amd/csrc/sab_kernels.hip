@@ -6,9 +6,15 @@
 // Only calc_pn and + - * / are involved, every output element is accumulated by
 // one thread in the reference's order, and the TU is always built with
 // -DNDPP_FAST=0 -ffp-contract=off: results are bit-identical to the Fortran.
+//
+// The tabular twins (ndpp_sab_tab_batch, include/ndpp_hip.h) follow the Legendre kernels: a
+// thermal table is a set of point masses, and a twin visits the same masses in the same order
+// and drops each, whole, into the bin of its cosine.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cfloat>
+#include <cmath>
 #include <vector>
 
 #include "../../include/ndpp_hip.h"
@@ -34,6 +40,7 @@ struct SabDev {
   const double* e_bins;
   const double* wgt;   // [NEo] discrete-mode weights (:167-186)
   double* distro;      // [NEi][G][L] continuous-mode table integrals (:281)
+  int* row_lost;       // [NEi] tabular, continuous mode: the table row holds a cosine that is not finite
   double* el;          // [NE][G][L]
   double* inel;
   double* mat;
@@ -229,6 +236,233 @@ __global__ void sab_combine_kernel(SabDev D) {
   }
 }
 
+// ---- tabular twins: D.L holds N, the number of lab-cosine bins --------------------------------
+// One block per incoming energy (stage 1 of the continuous mode: per (table E_in, group)), thread k
+// owns bin k of every group.  All lanes walk the masses together in the reference's order -- the
+// table reads are wave-uniform -- and the lane whose k is the mass's bin adds it to its own
+// element: every bin has one owner and one order of summation, nothing is shared between lanes.
+// Threads with k >= N never write.
+
+// The bin of a lab cosine: floor((mu + 1) * (0.5 * N)) clamped to 0 .. N-1, so that a cosine on an
+// interior edge goes up, mu = 1 into the last bin and a cosine rounded past +-1 into the end bin;
+// -1 for a cosine that is not finite (it goes into no bin).
+__device__ inline int sab_bin(double mu, int N) {
+  if (!(fabs(mu) <= DBL_MAX)) return -1;
+  const double q = floor((mu + 1.0) * (0.5 * (double)N));
+  return q < 0.0 ? 0 : (q > (double)(N - 1) ? N - 1 : (int)q);
+}
+
+// sab_el_kernel's order 0, bin by bin
+__global__ void sab_tab_el_kernel(SabDev D) {
+  const int N = D.L, k = threadIdx.x;
+  const bool own = k < N;
+  const ndpp_sab_flat& t = D.t;
+  for (int i = blockIdx.x; i < D.NE; i += gridDim.x) {
+    double* row = D.el + (size_t)i * D.G * N;
+    if (own) for (int g = 0; g < D.G; ++g) row[(size_t)g * N + k] = 0.0;
+    if (t.threshold_elastic == 0.0) continue;
+    const double Ein = D.ein[i];
+    if (Ein < t.elastic_e_in[0]) continue;
+    else if (Ein >= t.threshold_elastic) continue;
+    const int isab = bsearch1(t.elastic_e_in, t.n_elastic_e_in, Ein);
+    if (isab < 0) { if (k == 0) atomicOr(&D.status[i], NDPP_ST_RANGE); continue; }
+    const double f = (Ein - t.elastic_e_in[isab - 1]) / (t.elastic_e_in[isab] - t.elastic_e_in[isab - 1]);
+    if (Ein < D.e_bins[0]) continue;
+    else if (Ein > D.e_bins[D.G]) continue;
+    int g = bsearch1(D.e_bins, D.G + 1, Ein);
+    if (g < 1) g = 1;  // NaN energy: stay inside the row
+    double sig = 0.0;
+    if (t.elastic_mode == SAB_ELASTIC_EXACT) sig = t.elastic_P[isab - 1] / Ein;
+    else if (t.elastic_mode == SAB_ELASTIC_DISCRETE)
+      sig = (1.0 - f) * t.elastic_P[isab - 1] + f * t.elastic_P[isab];
+    double acc = 0.0;
+    bool lost = false;  // a cosine that is not finite
+    if (t.n_elastic_mu == 0) {
+      const int kb = sab_bin(1.0 - t.elastic_e_in[isab - 1] / Ein, N);  // coherent: one Bragg edge, :87
+      lost = kb < 0;
+      if (kb == k) acc = acc + 1.0;
+    } else if (t.elastic_mode == SAB_ELASTIC_DISCRETE) {
+      const int NMU = t.n_elastic_mu;
+      const double wgt = 1.0 / (double)NMU;
+      for (int imu = 0; imu < NMU; ++imu) {
+        const double mu = (1.0 - f) * t.elastic_mu[(size_t)(isab - 1) * NMU + imu] +
+                          f * t.elastic_mu[(size_t)isab * NMU + imu];
+        const int kb = sab_bin(mu, N);
+        lost = lost || kb < 0;
+        if (kb == k) acc = acc + wgt;
+      }
+    }
+    if (own) row[(size_t)(g - 1) * N + k] = sig * acc;
+    if (lost && k == 0) atomicOr(&D.status[i], NDPP_ST_NONFINITE);
+  }
+}
+
+// sab_inel_disc_kernel's order 0, bin by bin.  A group's bin stays in a register for as long as
+// the outgoing energies keep falling into that group and goes back to the row when they move on.
+__global__ void sab_tab_inel_disc_kernel(SabDev D) {
+  const int N = D.L, k = threadIdx.x;
+  const bool own = k < N;
+  const ndpp_sab_flat& t = D.t;
+  const int NEo = t.n_inelastic_e_out, NMU = t.n_inelastic_mu, NEi = t.n_inelastic_e_in;
+  for (int i = blockIdx.x; i < D.NE; i += gridDim.x) {
+    double* row = D.inel + (size_t)i * D.G * N;
+    if (own) for (int g = 0; g < D.G; ++g) row[(size_t)g * N + k] = 0.0;
+    const double Ein = D.ein[i];
+    int isab;
+    double f;
+    if (Ein < t.inelastic_e_in[0]) { isab = 1; f = 0.0; }
+    else if (Ein > t.threshold_inelastic) continue;
+    else if (Ein == t.threshold_inelastic) { isab = NEi - 1; f = 1.0; }
+    else {
+      isab = bsearch1(t.inelastic_e_in, NEi, Ein);
+      if (isab < 0) { if (k == 0) atomicOr(&D.status[i], NDPP_ST_RANGE); continue; }
+      f = (Ein - t.inelastic_e_in[isab - 1]) / (t.inelastic_e_in[isab] - t.inelastic_e_in[isab - 1]);
+    }
+    const double sig = (1.0 - f) * t.inelastic_sigma[isab - 1] + f * t.inelastic_sigma[isab];
+    int held = 0;       // the group (1-based) whose bin is in acc; 0: none yet
+    double acc = 0.0;
+    bool lost = false;  // a cosine that is not finite
+    for (int io = 0; io < NEo; ++io) {
+      const double Eout = (1.0 - f) * t.inelastic_e_out[(size_t)(isab - 1) * NEo + io] +
+                          f * t.inelastic_e_out[(size_t)isab * NEo + io];
+      if (Eout < D.e_bins[0]) continue;
+      else if (Eout >= D.e_bins[D.G]) continue;
+      int g = bsearch1(D.e_bins, D.G + 1, Eout);
+      if (g < 1) g = 1;  // NaN energy: stay inside the row
+      if (g != held) {
+        if (own && held) row[(size_t)(held - 1) * N + k] = acc;
+        acc = own ? row[(size_t)(g - 1) * N + k] : 0.0;
+        held = g;
+      }
+      const double w = D.wgt[io];
+      for (int imu = 0; imu < NMU; ++imu) {
+        const double mu = (1.0 - f) * t.inelastic_mu[((size_t)(isab - 1) * NEo + io) * NMU + imu] +
+                          f * t.inelastic_mu[((size_t)isab * NEo + io) * NMU + imu];
+        const int kb = sab_bin(mu, N);
+        lost = lost || kb < 0;
+        if (kb == k) acc = acc + w;
+      }
+    }
+    if (own) {
+      if (held) row[(size_t)(held - 1) * N + k] = acc;
+      for (int g = 0; g < D.G; ++g) row[(size_t)g * N + k] = sig * row[(size_t)g * N + k];
+    }
+    if (lost && k == 0) atomicOr(&D.status[i], NDPP_ST_NONFINITE);
+  }
+}
+
+// sab_cont_table_kernel's order 0, bin by bin: block per (table E_in, group).  D.row_lost[table
+// E_in] is set where one of the row's cosines is not finite.
+__global__ void sab_tab_cont_table_kernel(SabDev D) {
+  const ndpp_sab_flat& t = D.t;
+  const int N = D.L, kk = threadIdx.x, NMU = t.n_inelastic_mu;
+  const long tot = (long)t.n_inelastic_e_in * D.G;
+  for (long q = blockIdx.x; q < tot; q += gridDim.x) {
+    const int g = (int)(q % D.G), k = (int)(q / D.G);
+    const int o = t.cont_ptr[k], NEout = t.cont_ptr[k + 1] - o;
+    const double *Eo = t.cont_e_out + o, *pd0 = t.cont_pdf + o;
+    const double* mu_arr = t.cont_mu + (size_t)o * NMU;
+    auto pdf = [&](int j1) -> double {  // 1-based, :299-303
+      return (j1 == NEout) ? 0.0 : pd0[j1 - 1] * (Eo[j1] - Eo[j1 - 1]);
+    };
+    const double eg = D.e_bins[g], eg1 = D.e_bins[g + 1];
+    double acc = 0.0;
+    int iE_lo = 1, iE_hi = 0;
+    bool live = true, lost = false;
+    // the masses of outgoing point j1 blended with its upper neighbour by fr, each of weight mult
+    auto edge = [&](int j1, double fr, double mult) {
+      for (int imu = 0; imu < NMU; ++imu) {
+        const double mu = (1.0 - fr) * mu_arr[(size_t)(j1 - 1) * NMU + imu] + fr * mu_arr[(size_t)j1 * NMU + imu];
+        const int kb = sab_bin(mu, N);
+        lost = lost || kb < 0;
+        if (kb == kk) acc = acc + mult;
+      }
+    };
+    if (eg < Eo[0]) iE_lo = 1;
+    else if (eg >= Eo[NEout - 1]) live = false;
+    else {
+      iE_lo = bsearch1(Eo, NEout, eg);
+      if (iE_lo < 1) iE_lo = 1;
+      const double f_lo = (eg - Eo[iE_lo - 1]) / (Eo[iE_lo] - Eo[iE_lo - 1]);
+      edge(iE_lo, f_lo, f_lo * pdf(iE_lo));
+      iE_lo = iE_lo + 1;
+    }
+    if (live) {
+      if (eg1 < Eo[0]) live = false;
+      else if (eg1 >= Eo[NEout - 1]) iE_hi = NEout - 1;
+      else {
+        iE_hi = bsearch1(Eo, NEout, eg1);
+        if (iE_hi < 1) iE_hi = 1;
+        const double f_hi = (eg1 - Eo[iE_hi - 1]) / (Eo[iE_hi] - Eo[iE_hi - 1]);
+        edge(iE_hi, f_hi, f_hi * pdf(iE_hi));
+        iE_hi = iE_hi - 1;
+      }
+    }
+    if (live) {
+      for (int iE = iE_lo; iE <= iE_hi; ++iE) {
+        const double w = pdf(iE);
+        for (int imu = 0; imu < NMU; ++imu) {
+          const int kb = sab_bin(mu_arr[(size_t)(iE - 1) * NMU + imu], N);
+          lost = lost || kb < 0;
+          if (kb == kk) acc = acc + w;
+        }
+      }
+      acc = acc / (double)NMU;
+    }
+    if (kk < N) D.distro[(size_t)q * N + kk] = live ? acc : 0.0;
+    if (live && lost && kk == 0) atomicOr(&D.row_lost[k], 1);
+  }
+}
+
+// stage 2 is sab_cont_interp_kernel with N entries per group; this hands a table row's lost cosine
+// to the incoming energies that read the row: thread per E_in, sab_cont_interp_kernel's brackets
+__global__ void sab_tab_cont_status_kernel(SabDev D) {
+  const ndpp_sab_flat& t = D.t;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < D.NE; i += gridDim.x * blockDim.x) {
+    const double Ein = D.ein[i];
+    int lost = 0;
+    if (Ein <= t.inelastic_e_in[0]) lost = D.row_lost[0];
+    else if (Ein >= t.threshold_inelastic) lost = 0;
+    else {
+      const int isab = bsearch1(t.inelastic_e_in, t.n_inelastic_e_in, Ein);
+      if (isab >= 1) lost = D.row_lost[isab - 1] | D.row_lost[isab];
+    }
+    if (lost) atomicOr(&D.status[i], NDPP_ST_NONFINITE);
+  }
+}
+
+// combine_sab_grid with a group's bin sum in the place of its P0: s is the Kahan sum of el + inel
+// over the row in storage order.  Block of 64 per E_in: the row is read 64 entries at a time and
+// every lane sums them from shared memory in the same order.
+__global__ void sab_tab_combine_kernel(SabDev D) {
+  __shared__ double part[64];
+  const int GL = D.G * D.L, k0 = threadIdx.x;
+  for (int i = blockIdx.x; i < D.NE; i += gridDim.x) {
+    const int src = (i == D.NE - 1 && D.NE >= 2) ? i - 1 : i;
+    const double *e = D.el + (size_t)src * GL, *q = D.inel + (size_t)src * GL;
+    double* m = D.mat + (size_t)i * GL;
+    double s = 0.0, c = 0.0;
+    for (int base = 0; base < GL; base += 64) {
+      __syncthreads();
+      if (base + k0 < GL) part[k0] = e[base + k0] + q[base + k0];
+      __syncthreads();
+      const int n = min(64, GL - base);
+      for (int j = 0; j < n; ++j) {
+        const double y = part[j] - c;
+        const double tt = s + y;
+        c = (tt - s) - y;
+        s = tt;
+      }
+    }
+    if (s > 0.0) {
+      s = 1.0 / s;
+      for (int k = k0; k < GL; k += 64) m[k] = (e[k] + q[k]) * s;
+    } else {
+      for (int k = k0; k < GL; k += 64) m[k] = 0.0;
+    }
+  }
+}
+
 // apply_tol_scatt (scatt.F90:786-818): thread per incoming energy; both sum()s are
 // Kahan-compensated like flang's SUM intrinsic.
 __global__ void apply_tol_kernel(int L, int G, int n, double* data, double tol) {
@@ -247,6 +481,112 @@ __global__ void apply_tol_kernel(int L, int G, int n, double* data, double tol) 
   }
 }
 
+// ---- the host side ndpp_sab_batch and ndpp_sab_tab_batch share -------------------------------
+// the table's counts and mode
+int check_sab_counts(const ndpp_sab_flat* t) {
+  const int mode = t->secondary_mode;
+  if (t->n_inelastic_e_in < 2 || t->n_inelastic_mu < 1)
+    return fail(NDPP_EINVAL, "need >= 2 inelastic E_in and >= 1 cosine");
+  if (mode != SAB_SECONDARY_EQUAL && mode != SAB_SECONDARY_SKEWED && mode != SAB_SECONDARY_CONT)
+    return fail(NDPP_EINVAL, "secondary_mode=%d", mode);
+  if (mode == SAB_SECONDARY_SKEWED && t->n_inelastic_e_out <= 4)  // reference: fatal_error, sab.F90:183
+    return fail(NDPP_EINVAL, "skewed weighting needs more than 4 outgoing energies");
+  return NDPP_OK;
+}
+
+// the continuous mode's rows and the elastic grid
+int check_sab_arrays(const ndpp_sab_flat* t) {
+  if (t->secondary_mode == SAB_SECONDARY_CONT) {
+    if (!t->cont_ptr) return fail(NDPP_EINVAL, "continuous mode without cont_ptr");
+    if (t->cont_ptr[0] != 0) return fail(NDPP_EINVAL, "cont_ptr[0] must be 0");
+    for (int k = 0; k < t->n_inelastic_e_in; ++k)
+      if (t->cont_ptr[k + 1] - t->cont_ptr[k] < 2)
+        return fail(NDPP_EINVAL, "continuous row %d has < 2 outgoing energies", k);
+  }
+  if (t->threshold_elastic != 0.0 && t->n_elastic_e_in < 2)
+    return fail(NDPP_EINVAL, "elastic data needs >= 2 E_in");
+  return NDPP_OK;
+}
+
+// The table, the grid and the discrete-mode weights on the device, and the three results
+// [n_ein][G][L] (L: orders, or bins when tab).  The table has passed both checks above.
+struct SabStage {
+  DevBuf<double> ei, sig, eo, mu, ce, cp, cm, ee, eP, emu, ein, bins, w, distro, el, inel, mat;
+  DevBuf<int> cptr, st, row_lost;
+  size_t nout = 0;
+
+  int upload(const ndpp_sab_flat* t, int n_ein, const double* h_ein, int G, const double* e_bins, int L,
+             bool tab, SabDev& D) {
+    const int NEi = t->n_inelastic_e_in, NEo = t->n_inelastic_e_out, NMU = t->n_inelastic_mu;
+    const int mode = t->secondary_mode;
+    nout = (size_t)n_ein * G * L;
+    // discrete-mode weights, sab.F90:167-186 (sum() as flang evaluates it: Kahan)
+    std::vector<double> wgt(std::max(NEo, 1), 0.0);
+    if (mode == SAB_SECONDARY_EQUAL) {
+      for (int k = 0; k < NEo; ++k) wgt[k] = 1.0 / ((double)NEo * (double)NMU);
+    } else if (mode == SAB_SECONDARY_SKEWED) {
+      wgt[0] = 0.1; wgt[1] = 0.4;
+      for (int k = 2; k < NEo - 2; ++k) wgt[k] = 1.0;
+      wgt[NEo - 2] = 0.4; wgt[NEo - 1] = 0.1;
+      double s = 0.0, c = 0.0;
+      for (int k = 0; k < NEo; ++k) { const double y = wgt[k] - c, tt = s + y; c = (tt - s) - y; s = tt; }
+      const double den = s * (double)NMU;
+      for (int k = 0; k < NEo; ++k) wgt[k] = wgt[k] / den;
+    }
+    D.t = *t;
+    D.NE = n_ein; D.G = G; D.L = L;
+    NDPP_TRY(ei.upload(t->inelastic_e_in, NEi));
+    NDPP_TRY(sig.upload(t->inelastic_sigma, NEi));
+    if (mode != SAB_SECONDARY_CONT) {
+      NDPP_TRY(eo.upload(t->inelastic_e_out, (size_t)NEi * NEo));
+      NDPP_TRY(mu.upload(t->inelastic_mu, (size_t)NEi * NEo * NMU));
+    } else {
+      const size_t tot = (size_t)t->cont_ptr[NEi];
+      NDPP_TRY(cptr.upload(t->cont_ptr, NEi + 1));
+      NDPP_TRY(ce.upload(t->cont_e_out, tot));
+      NDPP_TRY(cp.upload(t->cont_pdf, tot));
+      NDPP_TRY(cm.upload(t->cont_mu, tot * NMU));
+    }
+    if (t->threshold_elastic != 0.0) {
+      NDPP_TRY(ee.upload(t->elastic_e_in, t->n_elastic_e_in));
+      NDPP_TRY(eP.upload(t->elastic_P, t->n_elastic_e_in));
+      if (t->n_elastic_mu > 0)
+        NDPP_TRY(emu.upload(t->elastic_mu, (size_t)t->n_elastic_e_in * t->n_elastic_mu));
+    }
+    NDPP_TRY(ein.upload(h_ein, n_ein));
+    NDPP_TRY(bins.upload(e_bins, G + 1));
+    NDPP_TRY(w.upload(wgt.data(), wgt.size()));
+    NDPP_TRY(distro.alloc((size_t)NEi * G * L));
+    NDPP_TRY(el.alloc(nout));
+    NDPP_TRY(inel.alloc(nout));
+    NDPP_TRY(mat.alloc(nout));
+    NDPP_TRY(st.alloc(n_ein));
+    NDPP_TRY(hipMemset(st.p, 0, sizeof(int) * n_ein));
+    if (tab) {
+      NDPP_TRY(row_lost.alloc(NEi));
+      NDPP_TRY(hipMemset(row_lost.p, 0, sizeof(int) * NEi));
+    }
+    D.t.inelastic_e_in = ei.p; D.t.inelastic_sigma = sig.p;
+    D.t.inelastic_e_out = eo.p; D.t.inelastic_mu = mu.p;
+    D.t.cont_ptr = cptr.p; D.t.cont_e_out = ce.p; D.t.cont_pdf = cp.p; D.t.cont_mu = cm.p;
+    D.t.elastic_e_in = ee.p; D.t.elastic_P = eP.p; D.t.elastic_mu = emu.p;
+    D.ein = ein.p; D.e_bins = bins.p; D.wgt = w.p; D.distro = distro.p; D.row_lost = row_lost.p;
+    D.el = el.p; D.inel = inel.p; D.mat = mat.p; D.status = st.p;
+    return NDPP_OK;
+  }
+
+  // after the kernels: wait for them and copy out what the caller asked for
+  int download(double* h_el, double* h_inel, double* h_mat, int* h_status, int n_ein) {
+    NDPP_TRY(hipGetLastError());
+    NDPP_TRY(hipDeviceSynchronize());
+    NDPP_TRY(mat.download(h_mat, nout));
+    if (h_el) NDPP_TRY(el.download(h_el, nout));
+    if (h_inel) NDPP_TRY(inel.download(h_inel, nout));
+    if (h_status) NDPP_TRY(st.download(h_status, n_ein));
+    return NDPP_OK;
+  }
+};
+
 }  // namespace
 }  // namespace ndpp
 
@@ -261,92 +601,62 @@ extern "C" int ndpp_sab_batch(const ndpp_params* p, const ndpp_sab_flat* t, int 
   if (G < 1 || n_ein < 0) return fail(NDPP_EINVAL, "G=%d n_ein=%d", G, n_ein);
   if (n_ein == 0) return NDPP_OK;
   if (!ein || !e_bins || !scatt_mat) return fail(NDPP_EINVAL, "NULL array argument");
-  const int NEi = t->n_inelastic_e_in, NEo = t->n_inelastic_e_out, NMU = t->n_inelastic_mu;
-  const int mode = t->secondary_mode;
-  if (NEi < 2 || NMU < 1) return fail(NDPP_EINVAL, "need >= 2 inelastic E_in and >= 1 cosine");
-  if (mode != SAB_SECONDARY_EQUAL && mode != SAB_SECONDARY_SKEWED && mode != SAB_SECONDARY_CONT)
-    return fail(NDPP_EINVAL, "secondary_mode=%d", mode);
-  if (mode == SAB_SECONDARY_SKEWED && NEo <= 4)  // reference: fatal_error, sab.F90:183
-    return fail(NDPP_EINVAL, "skewed weighting needs more than 4 outgoing energies");
+  if (int rc = check_sab_counts(t)) return rc;
   if (int rc = require_device()) return rc;
+  if (int rc = check_sab_arrays(t)) return rc;
 
-  const int L = p->order;
-  const size_t nout = (size_t)n_ein * G * L;
-  // discrete-mode weights, sab.F90:167-186 (sum() as flang evaluates it: Kahan)
-  std::vector<double> wgt(std::max(NEo, 1), 0.0);
-  if (mode == SAB_SECONDARY_EQUAL) {
-    for (int k = 0; k < NEo; ++k) wgt[k] = 1.0 / ((double)NEo * (double)NMU);
-  } else if (mode == SAB_SECONDARY_SKEWED) {
-    wgt[0] = 0.1; wgt[1] = 0.4;
-    for (int k = 2; k < NEo - 2; ++k) wgt[k] = 1.0;
-    wgt[NEo - 2] = 0.4; wgt[NEo - 1] = 0.1;
-    double s = 0.0, c = 0.0;
-    for (int k = 0; k < NEo; ++k) { const double y = wgt[k] - c, tt = s + y; c = (tt - s) - y; s = tt; }
-    const double den = s * (double)NMU;
-    for (int k = 0; k < NEo; ++k) wgt[k] = wgt[k] / den;
-  }
+  const int L = p->order, NEi = t->n_inelastic_e_in;
   SabDev D;
-  D.t = *t;
-  D.NE = n_ein; D.G = G; D.L = L;
-  DevBuf<double> d_ei, d_sig, d_eo, d_mu, d_ce, d_cp, d_cm, d_ee, d_eP, d_emu, d_ein, d_bins, d_w,
-      d_distro, d_el, d_inel, d_mat;
-  DevBuf<int> d_cptr, d_st;
-  NDPP_TRY(d_ei.upload(t->inelastic_e_in, NEi));
-  NDPP_TRY(d_sig.upload(t->inelastic_sigma, NEi));
-  if (mode != SAB_SECONDARY_CONT) {
-    NDPP_TRY(d_eo.upload(t->inelastic_e_out, (size_t)NEi * NEo));
-    NDPP_TRY(d_mu.upload(t->inelastic_mu, (size_t)NEi * NEo * NMU));
-  } else {
-    if (!t->cont_ptr) return fail(NDPP_EINVAL, "continuous mode without cont_ptr");
-    if (t->cont_ptr[0] != 0) return fail(NDPP_EINVAL, "cont_ptr[0] must be 0");
-    const size_t tot = (size_t)t->cont_ptr[NEi];
-    for (int k = 0; k < NEi; ++k)
-      if (t->cont_ptr[k + 1] - t->cont_ptr[k] < 2)
-        return fail(NDPP_EINVAL, "continuous row %d has < 2 outgoing energies", k);
-    NDPP_TRY(d_cptr.upload(t->cont_ptr, NEi + 1));
-    NDPP_TRY(d_ce.upload(t->cont_e_out, tot));
-    NDPP_TRY(d_cp.upload(t->cont_pdf, tot));
-    NDPP_TRY(d_cm.upload(t->cont_mu, tot * NMU));
-  }
-  if (t->threshold_elastic != 0.0) {
-    if (t->n_elastic_e_in < 2) return fail(NDPP_EINVAL, "elastic data needs >= 2 E_in");
-    NDPP_TRY(d_ee.upload(t->elastic_e_in, t->n_elastic_e_in));
-    NDPP_TRY(d_eP.upload(t->elastic_P, t->n_elastic_e_in));
-    if (t->n_elastic_mu > 0)
-      NDPP_TRY(d_emu.upload(t->elastic_mu, (size_t)t->n_elastic_e_in * t->n_elastic_mu));
-  }
-  NDPP_TRY(d_ein.upload(ein, n_ein));
-  NDPP_TRY(d_bins.upload(e_bins, G + 1));
-  NDPP_TRY(d_w.upload(wgt.data(), wgt.size()));
-  NDPP_TRY(d_distro.alloc((size_t)NEi * G * L));
-  NDPP_TRY(d_el.alloc(nout));
-  NDPP_TRY(d_inel.alloc(nout));
-  NDPP_TRY(d_mat.alloc(nout));
-  NDPP_TRY(d_st.alloc(n_ein));
-  NDPP_TRY(hipMemset(d_st.p, 0, sizeof(int) * n_ein));
-  D.t.inelastic_e_in = d_ei.p; D.t.inelastic_sigma = d_sig.p;
-  D.t.inelastic_e_out = d_eo.p; D.t.inelastic_mu = d_mu.p;
-  D.t.cont_ptr = d_cptr.p; D.t.cont_e_out = d_ce.p; D.t.cont_pdf = d_cp.p; D.t.cont_mu = d_cm.p;
-  D.t.elastic_e_in = d_ee.p; D.t.elastic_P = d_eP.p; D.t.elastic_mu = d_emu.p;
-  D.ein = d_ein.p; D.e_bins = d_bins.p; D.wgt = d_w.p; D.distro = d_distro.p;
-  D.el = d_el.p; D.inel = d_inel.p; D.mat = d_mat.p; D.status = d_st.p;
+  SabStage S;
+  if (int rc = S.upload(t, n_ein, ein, G, e_bins, L, false, D)) return rc;
 
   GpuSpan span(nullptr, kProfSab);
   hipLaunchKernelGGL(sab_el_kernel, dim3(nblk((long)n_ein * L, 128)), dim3(128), 0, 0, D);
-  if (mode == SAB_SECONDARY_CONT) {
+  if (t->secondary_mode == SAB_SECONDARY_CONT) {
     hipLaunchKernelGGL(sab_cont_table_kernel, dim3(nblk((long)NEi * G * L, 64)), dim3(64), 0, 0, D);
-    hipLaunchKernelGGL(sab_cont_interp_kernel, dim3(nblk((long)nout, 256)), dim3(256), 0, 0, D);
+    hipLaunchKernelGGL(sab_cont_interp_kernel, dim3(nblk((long)S.nout, 256)), dim3(256), 0, 0, D);
   } else {
     hipLaunchKernelGGL(sab_inel_disc_kernel, dim3(nblk((long)n_ein * L, 128)), dim3(128), 0, 0, D);
   }
   hipLaunchKernelGGL(sab_combine_kernel, dim3(nblk(n_ein, 128)), dim3(128), 0, 0, D);
   span.end();
-  NDPP_TRY(hipGetLastError());
-  NDPP_TRY(hipDeviceSynchronize());
-  NDPP_TRY(hipMemcpy(scatt_mat, d_mat.p, sizeof(double) * nout, hipMemcpyDeviceToHost));
-  if (el) NDPP_TRY(hipMemcpy(el, d_el.p, sizeof(double) * nout, hipMemcpyDeviceToHost));
-  if (inel) NDPP_TRY(hipMemcpy(inel, d_inel.p, sizeof(double) * nout, hipMemcpyDeviceToHost));
-  return NDPP_OK;
+  return S.download(el, inel, scatt_mat, nullptr, n_ein);
+}
+
+// The tabular twin: ndpp_sab_batch's checks (n_tab in the place of the order, which is not read),
+// all of them before the device is asked for.
+extern "C" int ndpp_sab_tab_batch(const ndpp_params* p, const ndpp_sab_flat* t, int n_tab, int n_ein,
+                                  const double* ein, int G, const double* e_bins, double* el,
+                                  double* inel, double* scatt_mat, int* status) {
+  if (!p || !t) return fail(NDPP_EINVAL, "NULL params/table");
+  if (n_tab < 1 || n_tab > NDPP_MAX_TAB_BINS)
+    return fail(NDPP_EINVAL, "n_tab=%d outside 1..%d", n_tab, NDPP_MAX_TAB_BINS);
+  if (G < 1 || n_ein < 0) return fail(NDPP_EINVAL, "G=%d n_ein=%d", G, n_ein);
+  if (n_ein == 0) return NDPP_OK;
+  if (!ein || !e_bins || !scatt_mat) return fail(NDPP_EINVAL, "NULL array argument");
+  if (int rc = check_sab_counts(t)) return rc;
+  if (int rc = check_sab_arrays(t)) return rc;
+  if (int rc = require_device()) return rc;
+
+  const int N = n_tab, NEi = t->n_inelastic_e_in;
+  SabDev D;
+  SabStage S;
+  if (int rc = S.upload(t, n_ein, ein, G, e_bins, N, true, D)) return rc;
+
+  const dim3 bins_block(N <= 64 ? 64 : 128);       // thread k owns bin k
+  static_assert(NDPP_MAX_TAB_BINS <= 128, "one thread per bin");
+  GpuSpan span(nullptr, kProfSab);
+  hipLaunchKernelGGL(sab_tab_el_kernel, dim3(nblk(n_ein, 1)), bins_block, 0, 0, D);
+  if (t->secondary_mode == SAB_SECONDARY_CONT) {
+    hipLaunchKernelGGL(sab_tab_cont_table_kernel, dim3(nblk((long)NEi * G, 1)), bins_block, 0, 0, D);
+    hipLaunchKernelGGL(sab_cont_interp_kernel, dim3(nblk((long)S.nout, 256)), dim3(256), 0, 0, D);
+    hipLaunchKernelGGL(sab_tab_cont_status_kernel, dim3(nblk(n_ein, 128)), dim3(128), 0, 0, D);
+  } else {
+    hipLaunchKernelGGL(sab_tab_inel_disc_kernel, dim3(nblk(n_ein, 1)), bins_block, 0, 0, D);
+  }
+  hipLaunchKernelGGL(sab_tab_combine_kernel, dim3(nblk(n_ein, 1)), dim3(64), 0, 0, D);
+  span.end();
+  return S.download(el, inel, scatt_mat, status, n_ein);
 }
 
 extern "C" int ndpp_apply_tol_scatt(int L, int G, int n, double* data, double tol) {

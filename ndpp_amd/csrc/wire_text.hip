@@ -342,7 +342,7 @@ extern "C" long ndpp_nuclide_file(const ndpp_output_options* o, const char* name
     return -1;
   }
   const bool tab = o->scatt_type == NDPP_SCATT_TABULAR;
-  if (tab && is_sab) {
+  if (tab && is_sab && is_sab != 2) {                               // 2: the caller asked for it
     fail(NDPP_EINVAL, "nuclide_file: tabular output of thermal S(alpha,beta) tables is not supported");
     return -1;
   }

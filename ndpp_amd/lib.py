@@ -45,7 +45,7 @@ EXPORTS = [
     "ndpp_lib_xml_nuclide", "ndpp_lib_xml_closer", "ndpp_finish_scatt", "ndpp_nuclide_file",
     "ndpp_scatt_positivity", "ndpp_expand_moments",
     "ndpp_elastic_tab_batch", "ndpp_file6_tab_batch", "ndpp_law9_tab_batch", "ndpp_scatt_nuclide_tab",
-    "ndpp_scatt_library_tab", "ndpp_scatt_library_at", "ndpp_grid_error",
+    "ndpp_scatt_library_tab", "ndpp_sab_tab_batch", "ndpp_scatt_library_at", "ndpp_grid_error",
     "ndpp_thin_segments", "ndpp_thin_bounded", "ndpp_lib_compare",
     "ndpp_scatt_minimum", "ndpp_scatt_minimum_evals", "ndpp_scatt_repair", "ndpp_scatt_repair_evals",
 ]
@@ -613,6 +613,9 @@ def load(build_if_missing: bool = False, torch_compat: bool | None = None) -> C.
     lib.ndpp_scatt_nuclide_tab.argtypes = [PP, C.c_int] + lib.ndpp_scatt_nuclide.argtypes[1:]
     lib.ndpp_scatt_library_tab.argtypes = [PP, C.c_int] + lib.ndpp_scatt_library.argtypes[1:]
     if not explicit:
+        # (the thermal one takes n_tab after the table, and a status array at the end)
+        lib.ndpp_sab_tab_batch.argtypes = [PP, C.POINTER(SabFlat), C.c_int] + lib.ndpp_sab_batch.argtypes[2:] + \
+                                          [c_int_p]
         c_double_pp = C.POINTER(c_double_p)
         lib.ndpp_scatt_library_at.argtypes = [PP, C.c_int, C.POINTER(AceNuclide), C.c_int, c_double_p, C.c_int,
                                               c_int_p, c_double_pp, c_int_p, c_double_pp, C.POINTER(ScattResult)]
@@ -859,6 +862,27 @@ def sab_batch(params: Params, table, ein, e_bins, want_parts: bool = False):
                                  _dp(el) if want_parts else None,
                                  _dp(inel) if want_parts else None, _dp(mat)))
     return (mat, el, inel) if want_parts else mat
+
+
+def sab_tab_batch(params: Params, n_tab, table, ein, e_bins, want_parts: bool = False, want_status: bool = False):
+    """ndpp_sab_tab_batch: sab_batch's P0 in n_tab lab-cosine bins, every discrete cosine's mass whole
+    in the bin that holds it (params.order is not read).  Returns scatt_mat[n_ein][G][n_tab], then
+    the elastic / inelastic parts (want_parts), then status[n_ein] (want_status)."""
+    t = table if isinstance(table, SabFlat) else SabFlat.from_dict(table)
+    ein, e_bins = _f64(ein), _f64(e_bins)
+    G = e_bins.shape[0] - 1
+    shape = (len(ein), G, max(int(n_tab), 0))
+    mat = np.zeros(shape)
+    el = np.zeros(shape) if want_parts else None
+    inel = np.zeros(shape) if want_parts else None
+    status = np.zeros(len(ein), dtype=np.int32) if want_status else None
+    _check(load().ndpp_sab_tab_batch(C.byref(params), C.byref(t), int(n_tab), len(ein), _dp(ein), G, _dp(e_bins),
+                                     _dp(el) if want_parts else None, _dp(inel) if want_parts else None,
+                                     _dp(mat), _ip(status) if want_status else None))
+    out = (mat, el, inel) if want_parts else (mat,)
+    if want_status:
+        out = out + (status,)
+    return out if len(out) > 1 else mat
 
 
 def apply_tol_scatt(data: np.ndarray, tol: float) -> np.ndarray:
@@ -1350,7 +1374,9 @@ def finish_scatt(opts: OutputOptions, result: dict, e_bins):
 
 def nuclide_file(opts: OutputOptions, name: str, kT, result: dict, e_bins, chi=None, is_sab=False) -> bytes:
     """ndpp_nuclide_file: one table's library file (header + scatter + chi sections).
-    chi: None or (e_grid, chi_t, chi_p, chi_d) as chi_batch returns them."""
+    chi: None or (e_grid, chi_t, chi_p, chi_d) as chi_batch returns them.  is_sab: False / 0 a
+    neutron table, True / 1 a thermal table (refused with scatt_type tabular), 2 a thermal table
+    whose matrix may be tabular (sab_tab_batch)."""
     e_bins = _f64(e_bins)
     r, keep = _scatt_struct(result)
     nm = name.encode()

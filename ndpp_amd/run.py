@@ -6,18 +6,30 @@ into <dir>, under the names and in the formats the reference's `ndpp <dir>` writ
 Every step goes through the C ABI (include/ndpp_hip.h):
   neutron tables   all in ONE scatt_library (scatt_library_tab for scatt_type tabular) call;
   chi              chi_egrid_lib + chi_batch per fissionable table (integrate_chi);
-  thermal tables   sab_egrid_lib (+ the extra top point) + sab_batch;
+  thermal tables   sab_egrid_lib (+ the extra top point) + sab_batch (sab_tab_batch with
+                   --thermal-tabular);
   every table      finish_scatt (print_tol, thinning when thinning_tol > 0), nuclide_file;
   the run          lib_xml.
 ndpp.xml is read with the reference's defaults (constants.F90) and refusals (ndpp.F90
 init_ndpp); `threads` is accepted and ignored; output_format hdf5 and human are refused (the
 library writes neither); tabular output of a thermal table is refused before anything is
-computed (ndpp_nuclide_file does not write it).
+computed unless --thermal-tabular asks for it (below).
 
 Exit status: 0 library written, 2 input error (nothing written), 3 library or device error
 (nothing written).  Files are written under temporary names and renamed once every table is
 done, so a failed run leaves no partial library.
---json FILE: one record per table (kind, incoming energies, wall time, device time).
+--json FILE: one record per table (kind, incoming energies, wall time, device time; `bins: N` for
+a thermal table written in bins).
+
+Thermal tables in bins (scatt_type tabular only; with scatt_type legendre the flag is an input
+error):
+  --thermal-tabular    the thermal tables go through sab_egrid_lib, the extra top point and
+                       sab_tab_batch with N = scatt_order, and are written with is_sab = 2: every
+                       discrete cosine's mass, whole, in the bin that holds it (include/ndpp_hip.h;
+                       DESIGN.md section 17).  Opt-in because a histogram of point masses moves mass
+                       from one bin to the next as E_in moves: such rows do not interpolate between
+                       grid points the way the neutron tables' rows do.  Without the flag a tabular
+                       run that lists a thermal table is refused, as before.
 
 Grid quality (ndpp_amd.gridcheck; Legendre output only, scatt_type tabular with either flag is an
 input error):
@@ -312,6 +324,7 @@ def compute(s: dict, tables: list, grid_opts: dict | None = None, repair_opts: d
     is returned: [dict(name, kind, report)] per table."""
     p, o, bins = params_of(s), options_of(s), s["energy_bins"]
     tab = s["scatt_type"] == "tabular"
+    th_tab = tab and bool(s.get("thermal_tabular"))         # --thermal-tabular: the thermal tables in bins too
     files, recs = [None] * len(tables), [None] * len(tables)
     go = grid_opts or {}
     raw, grid_rep = [None] * len(tables), None
@@ -381,14 +394,16 @@ def compute(s: dict, tables: list, grid_opts: dict | None = None, repair_opts: d
         lib.profile_reset()
         t0 = time.perf_counter()
         ein = grid.add_one_more_point(lib.sab_egrid_lib(p, d, bins))
-        mat = lib.sab_batch(p, d, ein, bins)
+        mat = lib.sab_tab_batch(p, s["scatt_order"], d, ein, bins) if th_tab else lib.sab_batch(p, d, ein, bins)
         wall, dev, last = time.perf_counter() - t0, _device_ms(), float(lib.load().ndpp_last_gpu_ms())
         raw[k] = dict(ein_el=ein, el_mat=mat, ein_inel=None, inel_mat=None, nuinel_mat=None)
         fin = finish(k, dict(ein_el=ein, el_mat=mat, ein_inel=None, inel_mat=None, nuinel_mat=None))
         if s["lib_format"] != lib.FMT_NONE:
-            files[k] = lib.nuclide_file(o, d["name"], d["kT"], fin, bins, is_sab=True)
+            files[k] = lib.nuclide_file(o, d["name"], d["kT"], fin, bins, is_sab=2 if th_tab else True)
         recs[k] = dict(name=t["listing"]["name"], kind="thermal", file=t["file"],
                        energies=dict(elastic=len(ein), inelastic=0), wall_s=wall, device_ms=dev, last_gpu_ms=last)
+        if th_tab:
+            recs[k]["bins"] = s["scatt_order"]
     out = [(t["file"], f) for t, f in zip(tables, files)]
     if go.get("check"):
         t1 = time.perf_counter()
@@ -450,12 +465,16 @@ def write_library(run_dir, files: list, xml: bytes) -> list:
 
 
 def run(run_dir, json_path=None, out=sys.stdout, grid_opts: dict | None = None,
-        repair_opts: dict | None = None) -> int:
+        repair_opts: dict | None = None, thermal_tabular: bool = False) -> int:
     """The whole driver; returns the exit status."""
     run_dir = Path(run_dir)
     t_start = time.perf_counter()
     try:
         s = read_ndpp_xml(run_dir)
+        if thermal_tabular and s["scatt_type"] != "tabular":
+            raise InputError("--thermal-tabular asks for the thermal tables of a tabular run in bins: give it with "
+                             "<scatt_type> tabular")
+        s["thermal_tabular"] = bool(thermal_tabular)
         if grid_opts is not None and s["scatt_type"] == "tabular":
             raise InputError("--check-grid, --refine-grid and --thin-grid cover Legendre output only: the tabular rows of the "
                              "free-gas range do not settle, so an error measured on them would be the "
@@ -473,7 +492,8 @@ def run(run_dir, json_path=None, out=sys.stdout, grid_opts: dict | None = None,
     try:
         lib.load()
         try:
-            _refuse_thermal_tabular(s, tables)
+            if not s["thermal_tabular"]:
+                _refuse_thermal_tabular(s, tables)
         except InputError as e:
             print(f"ndpp_amd.run: input error: {e}", file=sys.stderr)
             return EXIT_INPUT
@@ -604,6 +624,9 @@ def main(argv=None) -> int:
                     help="tolerance of the certificate, finite and >= 0 (default 1e-10)")
     ap.add_argument("--repair-undecided", action="store_true",
                     help="also repair rows whose minimum is within the tolerance of zero")
+    ap.add_argument("--thermal-tabular", action="store_true",
+                    help="with scatt_type tabular: write the thermal S(alpha,beta) tables in bins too, every "
+                         "discrete cosine's mass whole in its bin (without it such a run is refused)")
     a = ap.parse_args(argv)
     try:
         grid_opts = _grid_options(a)
@@ -611,7 +634,7 @@ def main(argv=None) -> int:
     except InputError as e:
         print(f"ndpp_amd.run: input error: {e}", file=sys.stderr)
         return EXIT_INPUT
-    return run(a.run_dir, a.json, grid_opts=grid_opts, repair_opts=repair_opts)
+    return run(a.run_dir, a.json, grid_opts=grid_opts, repair_opts=repair_opts, thermal_tabular=a.thermal_tabular)
 
 
 if __name__ == "__main__":
