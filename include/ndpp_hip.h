@@ -47,6 +47,13 @@ extern "C" {
 #define NDPP_ST_TAB_UNSETTLED 8 /* tabular free gas: an E' piece of the row did not settle to the
                                   error test within 128 panels (the finest estimate is kept) */
 
+/* per-event status of ndpp_scatt_sample (a value, not a bit set) */
+#define NDPP_SAMPLE_OK         0
+#define NDPP_SAMPLE_SKIPPED    1  /* E_in outside the grid or not positive and finite, or a u outside [0, 1) */
+#define NDPP_SAMPLE_BADROW     2  /* a negative or non-finite group mass, bin or moment in the blended row */
+#define NDPP_SAMPLE_ZEROROW    3  /* nothing scatters at this energy: every group mass is zero          */
+#define NDPP_SAMPLE_NEGDENSITY 4  /* Legendre: the density is negative at the cosine drawn (still returned) */
+
 #define NDPP_MAX_ORDER 11      /* L = scatt_order+1 <= 11 (ndpp.F90:290-301) */
 
 /* <scatt_type> (constants.F90, ndpp.F90:280-287): what a scattering row holds */
@@ -903,6 +910,67 @@ int ndpp_lib_compare(int G, int La, int Lb,
                      int nq, const double *xq,
                      double *err /* [nq] */, int *arg /* [nq] */,
                      double *worst /* [G][min(La,Lb)], may be NULL */);
+
+/* ---- sample an outgoing group and a scattering cosine from a section.
+ * Replaces nothing: the reference writes libraries and never reads a row the way a transport code
+ * does.  The section: x[n] strictly increasing, positive and finite, with the dense rows y[n][G][L] as
+ * ndpp_amd/reader.py's ScattSection.mat holds them; scatt_type NDPP_SCATT_LEGENDRE: L Legendre
+ * moments per group, 1 <= L <= NDPP_MAX_ORDER; NDPP_SCATT_TABULAR: L = N equal cosine bins per group,
+ * 1 <= N <= NDPP_MAX_TAB_BINS.  Event e has the incoming energy ein[e] and two uniform numbers
+ * u_g[e], u_mu[e] in [0, 1).  Every sum below starts from 0.0 and runs sequentially in ascending
+ * index; "blend(v0, v1) = v0 + (v1 - v0) * f".
+ * 1. Bracket (ndpp_lib_compare's rule and host code): i the largest index with x[i] <= ein,
+ *    i1 = min(i + 1, n - 1), f = ln(ein / x[i]) / ln(x[i1] / x[i]) with the host's log, f = 0 when
+ *    ein == x[i] (and at the last point).  An ein that is not positive and finite or lies outside
+ *    [x[0], x[n-1]], or a u_g or u_mu outside [0, 1) (a NaN included): status NDPP_SAMPLE_SKIPPED,
+ *    group -1, mu 0.
+ * 2. Group.  The mass of group g in the stored row r: s_r[g] = y[r][g][0] (Legendre), the sum over k
+ *    of y[r][g][k] (tabular).  w_g = blend(s_i[g], s_i1[g]), W = sum over g of w_g.  A w_g that is
+ *    negative or not finite, or a W that is not finite: NDPP_SAMPLE_BADROW, group -1, mu 0.
+ *    W == 0: NDPP_SAMPLE_ZEROROW, group -1, mu 0.  Otherwise group is the smallest g whose running
+ *    sum w_0 + ... + w_g exceeds u_g * W; if rounding leaves none, the last g with w_g > 0.  A group
+ *    with w_g = 0 is never drawn.
+ * 3. Cosine, tabular.  t_k = blend(y[i][g][k], y[i1][g][k]); a negative or non-finite t_k, or a sum
+ *    T of the t_k that is not finite: BADROW, group -1, mu 0; T == 0 (underflow only): ZEROROW alike.
+ *    target = u_mu * T; k is the smallest bin whose running sum c_k = t_0 + ... + t_k exceeds target,
+ *    else the last k with t_k > 0: a bin with t_k = 0 is never drawn.  With h = 2.0 / N,
+ *      mu = -1.0 + h * (k + (target - c_{k-1}) / t_k)            (c_{-1} = 0)
+ *    clamped to the bin [-1.0 + h * k, -1.0 + h * (k + 1)], whose right end is 1.0 for k = N - 1.
+ * 4. Cosine, Legendre.  a_l = blend(y[i][g][l], y[i1][g][l]), l < L; an a_l that is not finite:
+ *    BADROW, group -1, mu 0 (a_0 = w_g > 0 here).  The row's density is sum_l (l + 1/2) a_l P_l(mu),
+ *    its integral from -1
+ *      F(mu) = (0.5 * a_0) * (mu + 1.0) + sum over l = 1 .. L-1 of (0.5 * a_l) * (P_{l+1}(mu) - P_{l-1}(mu))
+ *    with F(1) = a_0, accumulated in ascending l, P by Bonnet's recurrence upwards in the order
+ *      P_0 = 1.0, P_1 = mu, P_{l+1} = (A_l * mu) * P_l - B_l * P_{l-1},
+ *      A_l = (double)(2 l + 1) / (double)(l + 1), B_l = (double)l / (double)(l + 1).
+ *    target = u_mu * a_0; lo = -1.0, hi = 1.0; 53 times: m = 0.5 * (lo + hi); if F(m) < target then
+ *    lo = m, else hi = m; mu = 0.5 * (lo + hi).  No moment problem is solved and nothing is assumed of
+ *    the row: on a positive row F is increasing and mu is the inverse of the CDF to the last bit of
+ *    the interval.  The density d = sum in ascending l (from 0.0) of ((l + 0.5) * a_l) * P_l(mu) is
+ *    evaluated once at the end: !(d >= 0) gives NDPP_SAMPLE_NEGDENSITY, with the group and the cosine
+ *    still returned -- such a row is not a distribution, and wants --repair-positivity
+ *    (ndpp_scatt_repair) before it is sampled.  The status is no positivity check: the bisection keeps
+ *    F(lo) < target <= F(hi) and so ends where F crosses the target upwards, where d is not negative;
+ *    a row with a dip inside (-1, 1) is sampled without a flag, and only a d that does not evaluate
+ *    (inf - inf) is caught.  ndpp_scatt_minimum decides whether a row is positive.
+ * 5. Otherwise status NDPP_SAMPLE_OK.
+ * i and f come from the host; + - * / and comparisons run on the device in the order written,
+ * without contraction: a host restatement reproduces group, mu and status bit for bit
+ * (ndpp_amd/sample.py: sample_numpy).
+ * NDPP_EINVAL, decided before the device is touched: a scatt_type other than 0 or 1, G < 1, L outside
+ * its range, n < 2, n_ev < 0, a NULL pointer, a grid that is not strictly increasing, positive and
+ * finite, sizes whose bytes overflow.  Without a device NDPP_EDEVICE; with one, n_ev == 0 is an empty
+ * success.                                                                                          */
+/* step 1 alone, the host half of ndpp_scatt_sample (which calls it): row[e] = i and weight[e] = f, or
+ * row[e] = -1 and weight[e] = 0 for an event that is skipped.  Needs no device.  For measurements
+ * (tools/bench_sample.py) and for a host that wants the brackets of its events.  NDPP_EINVAL: n < 2,
+ * n_ev < 0, a NULL pointer, a bad grid.                                                            */
+int ndpp_sample_brackets(int n, const double *x, long n_ev, const double *ein, const double *u_g,
+                         const double *u_mu, int *row /* [n_ev] */, double *weight /* [n_ev] */);
+int ndpp_scatt_sample(int scatt_type, int G, int L,
+                      int n, const double *x, const double *y /* [n][G][L] */,
+                      long n_ev, const double *ein, const double *u_g, const double *u_mu,
+                      int *group /* [n_ev] */, double *mu /* [n_ev] */, int *status /* [n_ev] */);
 
 #ifdef __cplusplus
 }

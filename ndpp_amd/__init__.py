@@ -19,7 +19,8 @@ from .lib import (_check, Params, Stats, NdppError, load, library_path, mu_grid,
                   HOW_HEAT, HOW_UNIFORM, HOW_UNREPAIRABLE, HOW_NONFINITE,
                   SCATT_LEGENDRE, SCATT_TABULAR, MAX_TAB_BINS, elastic_tab_batch, file6_tab_batch,
                   law9_tab_batch, sab_tab_batch, scatt_nuclide_tab, scatt_library_tab, scatt_library_at, grid_error,
-                  thin_segments, thin_bounded, lib_compare)
+                  thin_segments, thin_bounded, lib_compare,
+                  scatt_sample, sample_brackets, SAMPLE_OK, SAMPLE_SKIPPED, SAMPLE_BADROW, SAMPLE_ZEROROW, SAMPLE_NEGDENSITY)
 from .scatt import binary_search, elastic_brackets, calc_elastic_grid  # noqa: F401
 
 __version__ = "0.2.0"

@@ -130,13 +130,6 @@ compare_fold_kernel(int GLc, int n_chunks, const double* __restrict__ part, doub
   worst[e] = w;
 }
 
-// the largest i with x[i] <= v and the weight of row i + 1; v inside [x[0], x[n-1]]
-void bracket(int n, const double* x, double v, int* i_out, double* f_out) {
-  const int i = (int)(std::upper_bound(x, x + n, v) - x) - 1;
-  *i_out = i;
-  *f_out = (v == x[i] || i == n - 1) ? 0.0 : lne_weight(x[i], x[i + 1], v);
-}
-
 }  // namespace
 }  // namespace ndpp
 

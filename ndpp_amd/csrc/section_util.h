@@ -1,6 +1,7 @@
 // section_util.h -- what the analyses of a finished library share: expand_kernels.hip (sampled
 // positivity), minimum_kernels.hip (certified minimum), grid_kernels.hip (midpoint check),
-// compare_kernels.hip (two libraries) and thin_kernels.hip (error-bounded thinning).  The rules below
+// compare_kernels.hip (two libraries) and thin_kernels.hip (error-bounded thinning); sample_kernels.hip
+// (sampling) takes its bracket and its grid checks from here.  The rules below
 // are defined HERE, once; the files describe their own layout and point to this header.
 //
 // The band of an incoming energy: its groups from the first to the last with P0 > 0.  Only these rows
@@ -69,6 +70,14 @@ inline int check_gl_index(const char* who, int G, int L) {
 
 // the weight of row x1 at xm in [x0, x1], linear in ln E (the rule thin_grid assumes, thin.hip)
 inline double lne_weight(double x0, double x1, double xm) { return std::log(xm / x0) / std::log(x1 / x0); }
+
+// the rows a consumer reads at v inside [x[0], x[n-1]] (ndpp_lib_compare, ndpp_scatt_sample): the
+// largest i with x[i] <= v, and the weight of row i + 1
+inline void bracket(int n, const double* x, double v, int* i_out, double* f_out) {
+  const int i = (int)(std::upper_bound(x, x + n, v) - x) - 1;
+  *i_out = i;
+  *f_out = (v == x[i] || i == n - 1) ? 0.0 : lne_weight(x[i], x[i + 1], v);
+}
 
 // closes the span of an entry point's kernels and waits for them; a failure returns from the
 // entry point through NDPP_TRY, which names the call that failed

@@ -27,6 +27,9 @@ NDPP_ENOMEM = -12
 NDPP_EINVAL = -22
 NDPP_EOVERFLOW = -75
 NDPP_MAX_ORDER = 11
+NDPP_MAX_TAB_BINS = 128
+# per-event status of ndpp_scatt_sample
+SAMPLE_OK, SAMPLE_SKIPPED, SAMPLE_BADROW, SAMPLE_ZEROROW, SAMPLE_NEGDENSITY = 0, 1, 2, 3, 4
 
 EXPORTS = [
     "ndpp_default_params", "ndpp_version", "ndpp_last_error", "ndpp_last_gpu_ms",
@@ -48,6 +51,7 @@ EXPORTS = [
     "ndpp_scatt_library_tab", "ndpp_sab_tab_batch", "ndpp_scatt_library_at", "ndpp_grid_error",
     "ndpp_thin_segments", "ndpp_thin_bounded", "ndpp_lib_compare",
     "ndpp_scatt_minimum", "ndpp_scatt_minimum_evals", "ndpp_scatt_repair", "ndpp_scatt_repair_evals",
+    "ndpp_scatt_sample", "ndpp_sample_brackets",
 ]
 
 
@@ -637,6 +641,10 @@ def load(build_if_missing: bool = False, torch_compat: bool | None = None) -> C.
         lib.ndpp_scatt_repair_evals.argtypes = [C.c_int, C.c_int, C.c_int, c_double_p, C.c_int, C.c_int, C.c_int,
                                                 C.c_double, c_double_p, c_double_p, c_int_p, c_int_p,
                                                 C.POINTER(Repair)]
+        lib.ndpp_scatt_sample.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, c_double_p, c_double_p, C.c_long,
+                                          c_double_p, c_double_p, c_double_p, c_int_p, c_double_p, c_int_p]
+        lib.ndpp_sample_brackets.argtypes = [C.c_int, c_double_p, C.c_long, c_double_p, c_double_p, c_double_p,
+                                             c_int_p, c_double_p]
     _lib = lib
     return lib
 
@@ -1042,6 +1050,38 @@ def lib_compare(xa, ya, xb, yb, xq):
     _check(load().ndpp_lib_compare(G, La, Lb, na, _dp(xa), _dp(ya), nb, _dp(xb), _dp(yb), nq, _dp(xq), _dp(err),
                                    _ip(arg), _dp(worst)))
     return err[:nq], arg[:nq], worst
+
+
+def scatt_sample(scatt_type, x, y, ein, u_g, u_mu):
+    """ndpp_scatt_sample: per event (ein, u_g, u_mu) the outgoing group and the scattering cosine drawn
+    from the section x[n], y[n][G][L] (scatt_type 0: L Legendre moments, 1: L equal cosine bins) read
+    linearly in ln E (include/ndpp_hip.h).  Returns (group[n_ev] int32, mu[n_ev], status[n_ev] int32);
+    status is one of SAMPLE_OK, SAMPLE_SKIPPED, SAMPLE_BADROW, SAMPLE_ZEROROW, SAMPLE_NEGDENSITY."""
+    x, y = _f64(x), _f64(y)
+    ein, u_g, u_mu = _f64(ein).ravel(), _f64(u_g).ravel(), _f64(u_mu).ravel()
+    if y.ndim != 3 or x.shape != (y.shape[0],):
+        raise ValueError(f"x must be (n,) and y (n, G, L), got {x.shape} and {y.shape}")
+    if not (len(ein) == len(u_g) == len(u_mu)):
+        raise ValueError(f"ein, u_g and u_mu must have one length, got {len(ein)}, {len(u_g)}, {len(u_mu)}")
+    n, G, L = y.shape
+    n_ev = len(ein)
+    group, mu = np.zeros(max(n_ev, 1), dtype=np.int32), np.zeros(max(n_ev, 1))
+    status = np.zeros(max(n_ev, 1), dtype=np.int32)
+    _check(load().ndpp_scatt_sample(int(scatt_type), G, L, n, _dp(x), _dp(y), n_ev, _dp(ein), _dp(u_g), _dp(u_mu),
+                                    _ip(group), _dp(mu), _ip(status)))
+    return group[:n_ev], mu[:n_ev], status[:n_ev]
+
+
+def sample_brackets(x, ein, u_g, u_mu):
+    """ndpp_sample_brackets: (row[n_ev] int32, weight[n_ev]) of the events, the host half of
+    ndpp_scatt_sample; row -1: the event is skipped.  Needs no device."""
+    x, ein, u_g, u_mu = _f64(x), _f64(ein).ravel(), _f64(u_g).ravel(), _f64(u_mu).ravel()
+    if not (len(ein) == len(u_g) == len(u_mu)):
+        raise ValueError(f"ein, u_g and u_mu must have one length, got {len(ein)}, {len(u_g)}, {len(u_mu)}")
+    n_ev = len(ein)
+    row, weight = np.zeros(max(n_ev, 1), dtype=np.int32), np.zeros(max(n_ev, 1))
+    _check(load().ndpp_sample_brackets(len(x), _dp(x), n_ev, _dp(ein), _dp(u_g), _dp(u_mu), _ip(row), _dp(weight)))
+    return row[:n_ev], weight[:n_ev]
 
 
 def _thin_args(x, y, y2, tokeep):
