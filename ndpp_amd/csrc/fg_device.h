@@ -108,11 +108,28 @@ __global__ void fg_prep_kernel(FgBatch B, int level) {
     fg_prep_task(B, level, base, t);
 }
 
+// The item records of the level (fg_pipeline.h fg_item_build), one thread per inner integral of the
+// task order: after the level's sort, before its walk.
+template <int R>
+__global__ void fg_item_kernel(FgBatch B, int level) {
+  if (*B.overflow) return;
+  const int base = B.lvl_off(level);
+  const int nt = B.n_mu_tasks(level);
+  if (nt > B.icap) {                     // more records than there is room for: as when the arena runs out
+    if (blockIdx.x == 0 && threadIdx.x == 0) *B.overflow = 1;
+    return;
+  }
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < nt; i += gridDim.x * blockDim.x)
+    fg_item_build<R>(B, level, base, i, i);
+}
+
 // The hot loop.  Each lane owns one inner integral (kPath: one segment of one) at a
 // time and fetches the next from a global counter when done, so a wave only idles
 // lanes when the level runs out of work.
+// nt: the level's work items; kPath: kSplit per inner integral, item t = item t / nti of integral
+// t % nti, where nti = nt / kSplit
 template <int R, int LMAX, bool kPath>
-__device__ __forceinline__ void mu_wave_loop(const FgBatch& B, int level, int base, int nt,
+__device__ __forceinline__ void mu_wave_loop(const FgBatch& B, int nt,
                                              int* counter, DevMuStack<R>& st) {
   MuLane<R, LMAX> s;
   s.mask = 0;
@@ -126,12 +143,18 @@ __device__ __forceinline__ void mu_wave_loop(const FgBatch& B, int level, int ba
   // orders however long each one takes, and the per-order blocks of the others are skipped.
   const int kTaskBlock = nt >= (int)(gridDim.x * 16 * kWave) ? 4 * kWave : kWave;
   int blk_next = 0, blk_end = 0;          // wave-uniform
-  // Fetching costs the whole wave the set-up of an integral (~half a step).  The single-lane walk
-  // pays it every ~50 steps; the split walk's items are 20x shorter, so there the wave waits until
-  // kFetchMin lanes are free (or none is busy) and sets them up together.  (12 500-energy shard of
-  // the headline grid, 25 items per integral: 1523 ms fetching per free lane, 1421 ms waiting for 8,
-  // 1425 for 16, 1506 for 32; 16 equal items: 1481 / 1416 / 1424.)
-  constexpr int kFetchMin = kPath ? 8 : 1;
+  // split walk: the block's first item is item blk_rank of integral blk_rem (divided once per block, for
+  // the whole wave; a lane adds its offset)
+  const int nti = kPath ? nt >> kSplitLog2 : nt;
+  int blk_first = 0, blk_rank = 0, blk_rem = 0;
+  // Fetching costs the whole wave the set-up of the lanes that fetch.  The single-lane walk pays it every
+  // ~50 steps per lane; the split walk's items are 20x shorter, so there the wave waits until kFetchMin
+  // lanes are free (or none is busy) and sets them up together.  With the set-up read from item records
+  // (fg_item_build) waiting for 2, 4 or 8 is the same on the headline (1901 ms per pass each; 1927 fetching
+  // per free lane, 1972 waiting for 16) and a 12 500-energy shard prefers few (416 / 419 / 424 / 429 / 434 ms
+  // at 1 / 2 / 4 / 8 / 16).  When every lane gathered its own set-up, 8 was best on both (headline 2075 /
+  // 1992 / 1966 / 2014 ms at 2 / 4 / 8 / 16; profiles/item_records/README.md).
+  constexpr int kFetchMin = kPath ? 2 : 1;
   // (lane masks through the boolean ballot builtin: HIP's __ballot / __any go through an integer
   // select and a second comparison, two vector instructions each, in every iteration)
   auto lanes = [](bool x) -> unsigned long long { return __builtin_amdgcn_ballot_w64(x); };
@@ -147,13 +170,28 @@ __device__ __forceinline__ void mu_wave_loop(const FgBatch& B, int level, int ba
         blk_next = b;
         blk_end = (b + kTaskBlock < nt) ? b + kTaskBlock : nt;
         if (b >= nt) more = false;         // the level is handed out
+        if (kPath && more) {
+          blk_first = b;
+          blk_rank = b / nti;
+          blk_rem = b - blk_rank * nti;
+        }
       }
       if (!active && more) {
-        const int rank = __popcll(need & ((1ull << threadIdx.x) - 1ull));
-        const int t = blk_next + rank;
+        const int t = blk_next + __popcll(need & ((1ull << threadIdx.x) - 1ull));
         if (t < blk_end) {
-          if (kPath) mu_init_split<R, LMAX>(B, level, base, t, s);
-          else mu_init<R, LMAX>(B, level, base, t, s);
+          if (kPath) {
+            // a block that is no longer than an integral's run of items wraps at most once
+            int i = blk_rem + (t - blk_first), rank = blk_rank;
+            if (nti >= 4 * kWave) {
+              if (i >= nti) { i -= nti; rank += 1; }
+            } else {
+              rank = t / nti;
+              i = t - rank * nti;
+            }
+            mu_init_split<R, LMAX>(B, i, rank, s);
+          } else {
+            mu_init<R, LMAX>(B, t, s);
+          }
           active = (s.mask != 0);
           if (kPath) counts = (s.path_bits == 0);
           if (active) mu_tot_zero(s);
@@ -216,11 +254,10 @@ __global__ __launch_bounds__(kWave, kMuWavesPerSimd) void fg_mu_kernel(FgBatch B
   st.d0 = B.mu_its > kLevels ? B.mu_its - kLevels : 0;
 
   if (*B.overflow) return;
-  const int base = B.lvl_off(level);
   if (B.split_level(level))
-    mu_wave_loop<R, LMAX, true>(B, level, base, B.n_mu_tasks(level) * kSplit, counter, st);
+    mu_wave_loop<R, LMAX, true>(B, B.n_mu_tasks(level) * kSplit, counter, st);
   else
-    mu_wave_loop<R, LMAX, false>(B, level, base, B.n_mu_tasks(level), counter, st);
+    mu_wave_loop<R, LMAX, false>(B, B.n_mu_tasks(level), counter, st);
 }
 
 // split levels: the segment slots of the level's integrals start at zero (a slot is written by the
@@ -302,6 +339,10 @@ inline void launch_fg_setup(const FgBatch& B, hipStream_t s) {
 }
 inline void launch_fg_prep(const FgBatch& B, int level, hipStream_t s) {
   hipLaunchKernelGGL(fg_prep_kernel, dim3(2048), dim3(256), 0, s, B, level);
+}
+inline void launch_fg_item(const FgBatch& B, int level, hipStream_t s) {
+  if (B.R == 2) hipLaunchKernelGGL(fg_item_kernel<2>, dim3(2048), dim3(256), 0, s, B, level);
+  else hipLaunchKernelGGL(fg_item_kernel<1>, dim3(2048), dim3(256), 0, s, B, level);
 }
 inline void launch_fg_seg_zero(const FgBatch& B, int level, hipStream_t s) {
   hipLaunchKernelGGL(fg_seg_zero_kernel, dim3(4096), dim3(256), 0, s, B, level);

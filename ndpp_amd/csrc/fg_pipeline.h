@@ -76,6 +76,23 @@ constexpr int kMaxRows = 2;      // tabulated rows integrated jointly per incomi
 constexpr int kSplitLog2 = 4;
 constexpr int kSplit = 1 << kSplitLog2;          // segments (= summation slots = work items) per inner integral
 constexpr int kRowBits = 16;     // channel (row r, order l) <-> mask bit r*kRowBits + l
+// Fields of an item record (FgBatch::it_d / it_i).  Doubles: the mu limits a and b, K of each row at
+// a, b and the midpoint, then what the walk of this arithmetic reads of the FgPair of the integral's
+// (E_in, E_out) (item_pair_store): four members in the product's, nine in the reference's.  Ints: see ItemInt.
+constexpr int kItemA = 0, kItemB = 1, kItemXa = 2, kItemXb = kItemXa + kMaxRows, kItemXc = kItemXb + kMaxRows;
+constexpr int kItemPair = kItemXc + kMaxRows;
+constexpr int kItemPairFast = 4, kItemPairStrict = 9;
+constexpr int kItemDoublesFast = kItemPair + kItemPairFast, kItemDoublesStrict = kItemPair + kItemPairStrict;
+#if NDPP_FAST
+constexpr int kItemDoubles = kItemDoublesFast;
+#else
+constexpr int kItemDoubles = kItemDoublesStrict;
+#endif
+// kItemMask: the channels the walk integrates -- the node's, less the rows the Gauss stage took (0 =
+// nothing to walk: the fields after kItemNodeSlot are then not written); kItemNodeSlot: node * 8 + point
+// slot, where the result goes; kItemOff: FRows::off of the job's rows; kItemJp: the depth-kSplitLog2 node
+// the kernel's peak falls into (mu_init_split)
+enum ItemInt { kItemMask = 0, kItemNodeSlot, kItemOff, kItemJp, kItemInts };
 
 enum { kStatKEvals = 0, kStatMuVisits, kStatMuIntegrals, kStatEoutNodes,
        kStatWaveIters, kStatLaneIters, kStatOrderVisits, kStatGaussIntegrals, kNumStats };
@@ -155,6 +172,14 @@ struct FgBatch {
   // flags an aliased task in t_gl (kGaussAlias) as one whose rows are all done, which is how the
   // sort weight, the walk and the combine come to leave it alone: the table needs t_gl.
   int* t_alias = nullptr;
+  // ---- item records of the current level (fg_item_build): what the walk's set-up needs of inner
+  // integral i of the task order, [field][i] with tcap entries per field, so that the lanes of a wave
+  // (which take consecutive i) read every field as one run
+  // icap: records there is room for.  A level with more inner integrals to walk raises *overflow like a
+  // level that outgrows the arena (the chunk is redone with fewer energies).
+  int icap = 0;
+  double* it_d = nullptr;   // [kItemDoubles][icap]
+  int* it_i = nullptr;      // [kItemInts][icap]
 
   NDPP_HD double A_of(int job) const { return job_A ? job_A[job] : A; }
   NDPP_HD double kT_of(int job) const { return job_kT ? job_kT[job] : kT; }
@@ -185,6 +210,8 @@ struct FgBatch {
   }
   NDPP_HD double& S(int ch, int n) const { return node_S[(size_t)ch * ncap + n]; }
   NDPP_HD double& tX(int k, int r, int t) const { return t_X[((size_t)(k * R + r)) * tcap + t]; }
+  NDPP_HD double& itd(int field, int i) const { return it_d[(size_t)field * icap + i]; }
+  NDPP_HD int& iti(int field, int i) const { return it_i[(size_t)field * icap + i]; }
   NDPP_HD unsigned full_mask() const {
     unsigned m = 0;
     for (int r = 0; r < R; ++r) m |= ((1u << L) - 1u) << (r * kRowBits);
@@ -905,13 +932,84 @@ NDPP_HD int popcount32(unsigned x) {
 #endif
 }
 
-template <int R, int LMAX>
-NDPP_HD void mu_init(const FgBatch& B, int level, int base, int t, MuLane<R, LMAX>& s) {
+// What the walk reads of the FgPair of an inner integral.  The product's kernel value (fg_E2 and the
+// factor C1) needs four of its members; the members the reference's expressions are written in are
+// not kept in its records (and read as zero in a lane's copy: nothing in the walk looks at them).
+NDPP_HD void item_pair_store(const FgBatch& B, int i, const FgPair& q) {
+  int k = kItemPair;
+#if NDPP_FAST
+  B.itd(k++, i) = q.C1; B.itd(k++, i) = q.p; B.itd(k++, i) = q.q; B.itd(k++, i) = q.beta;
+#else
+  B.itd(k++, i) = q.s1; B.itd(k++, i) = q.c2; B.itd(k++, i) = q.kT; B.itd(k++, i) = q.EpE;
+  B.itd(k++, i) = q.s2; B.itd(k++, i) = q.AkT; B.itd(k++, i) = q.beta;
+  B.itd(k++, i) = q.inv_AkT; B.itd(k++, i) = q.inv_kT;
+#endif
+}
+NDPP_HD FgPair item_pair_load(const FgBatch& B, int i) {
+  FgPair q{};
+  int k = kItemPair;
+#if NDPP_FAST
+  q.C1 = B.itd(k++, i); q.p = B.itd(k++, i); q.q = B.itd(k++, i); q.beta = B.itd(k++, i);
+#else
+  q.s1 = B.itd(k++, i); q.c2 = B.itd(k++, i); q.kT = B.itd(k++, i); q.EpE = B.itd(k++, i);
+  q.s2 = B.itd(k++, i); q.AkT = B.itd(k++, i); q.beta = B.itd(k++, i);
+  q.inv_AkT = B.itd(k++, i); q.inv_kT = B.itd(k++, i);
+#endif
+  return q;
+}
+
+// The item record of inner integral i of the level's task order (one thread per i, after the level's
+// sort), written to entry `at` of the records (the device pipeline: at = i): everything of the walk's set-up that does not depend on which of the integral's work items a
+// lane takes.  The gathers through the task order, the node and the job happen here, at full
+// occupancy, instead of in the walk, where they stall a whole wave.
+template <int R>
+NDPP_HD void fg_item_build(const FgBatch& B, int level, int base, int i, int at) {
   int n, slot;
-  fg_task_decode(B, level, base, t, n, slot);
-  s.node = n;
-  s.slot = slot;
-  s.mask = (unsigned)B.node_info[4 * n + 0] & MuLane<R, LMAX>::kChanMask;
+  fg_task_decode(B, level, base, i, n, slot);
+  B.iti(kItemNodeSlot, at) = (int)((unsigned)n * 8u + (unsigned)slot);    // (n < 2^31 / 5)
+  unsigned mask = (unsigned)B.node_info[4 * n + 0];
+  const int rec = B.rec_index(level, base, n, slot);
+  if (mask != 0 && B.t_gl) {                                // rows done by the Gauss rule (mu_gauss_task)
+    const unsigned rows = B.t_gl[rec];
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+      if (rows >> r & 1u) mask &= ~(((1u << kRowBits) - 1u) << (r * kRowBits));
+  }
+  B.iti(kItemMask, at) = (int)mask;
+  if (mask == 0) return;
+  const int job = B.node_job(n);
+  const double Ein = B.job_ein[job];
+  const double Eout = fg_slot_point(B.node_a[n], B.node_b[n], slot);
+  const FgPair q = make_pair(B.A_of(job), B.kT_of(job), Ein, Eout);
+  item_pair_store(B, at, q);
+  // (a two-row job's rows are row_lo and row_lo + 1: make_jobs_kernel)
+  B.iti(kItemOff, at) = (int)(8u * (unsigned)B.M * (unsigned)B.job_row[(size_t)job * R]);
+  const double a = B.t_mulo[rec], b = B.t_muhi[rec];
+  B.itd(kItemA, at) = a;
+  B.itd(kItemB, at) = b;
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    B.itd(kItemXa + r, at) = B.tX(0, r, rec);
+    B.itd(kItemXb + r, at) = B.tX(1, r, rec);
+    B.itd(kItemXc + r, at) = B.tX(2, r, rec);
+  }
+  // the depth-kSplitLog2 node that holds the peak of the kernel (mu_init_split)
+#if NDPP_FAST
+  const double pa = q.p, qa = q.q;
+#else
+  const double pa = q.EpE / q.AkT, qa = 2.0 * q.s2 / q.AkT;
+#endif
+  const double x = ((pa - fabs(q.beta)) / qa - a) / (b - a) * (double)kSplit;
+  B.iti(kItemJp, at) = (x > 0.0) ? (x < (double)(kSplit - 1) ? (int)x : kSplit - 1) : 0;   // (NaN: 0)
+}
+
+// a lane's state at the root of inner integral i, from its item record
+template <int R, int LMAX>
+NDPP_HD void mu_init(const FgBatch& B, int i, MuLane<R, LMAX>& s) {
+  s.mask = (unsigned)B.iti(kItemMask, i) & MuLane<R, LMAX>::kChanMask;
+  const unsigned ns = (unsigned)B.iti(kItemNodeSlot, i);
+  s.node = (int)(ns >> 3);
+  s.slot = (int)(ns & 7u);
   s.pending = 0;
   s.depth = 0;
   s.visits = 0;
@@ -919,32 +1017,19 @@ NDPP_HD void mu_init(const FgBatch& B, int level, int base, int t, MuLane<R, LMA
 #pragma unroll
   for (int ch = 0; ch < R * LMAX; ++ch) s.acc[ch] = 0.0;   // (the caller zeroes the segment totals)
   s.path_left = 0; s.own_from = 0; s.path_bits = 0; s.own_pending = false; s.slot_path = 0;
-  s.task = t;
+  s.task = i;
   s.chans = s.mask;
   if (s.mask == 0) return;
-  const int rec = B.rec_index(level, base, n, slot);
-  if (B.t_gl) {                                             // rows done by the Gauss rule (mu_gauss_task)
-    const unsigned rows = B.t_gl[rec];
-#pragma unroll
-    for (int r = 0; r < R; ++r)
-      if (rows >> r & 1u) s.mask &= ~(((1u << kRowBits) - 1u) << (r * kRowBits));
-    s.chans = s.mask;
-    if (s.mask == 0) return;
-  }
-  const int job = B.node_job(n);
-  const double Ein = B.job_ein[job];
-  const double Eout = fg_slot_point(B.node_a[n], B.node_b[n], slot);
-  s.q = make_pair(B.A_of(job), B.kT_of(job), Ein, Eout);
-  // (a two-row job's rows are row_lo and row_lo + 1: make_jobs_kernel)
-  s.f.off = 8u * (unsigned)B.M * (unsigned)B.job_row[(size_t)job * R];
-  s.a = B.t_mulo[rec];
-  s.b = B.t_muhi[rec];
+  s.q = item_pair_load(B, i);
+  s.f.off = (unsigned)B.iti(kItemOff, i);
+  s.a = B.itd(kItemA, i);
+  s.b = B.itd(kItemB, i);
   double Xa[R];
 #pragma unroll
   for (int r = 0; r < R; ++r) {
-    Xa[r] = B.tX(0, r, rec);
-    s.Xb[r] = B.tX(1, r, rec);
-    s.Xc[r] = B.tX(2, r, rec);
+    Xa[r] = B.itd(kItemXa + r, i);
+    s.Xb[r] = B.itd(kItemXb + r, i);
+    s.Xc[r] = B.itd(kItemXc + r, i);
   }
   const double h = s.b - s.a;
   s.wp = h / 6.0;
@@ -1243,36 +1328,58 @@ NDPP_HD void mu_finish(const FgBatch& B, const MuLane<R, LMAX>& s, bool split = 
 // integrals start together at the beginning of the level and what is left for its end are the
 // cheap far nodes.  (Results do not depend on the order: every segment of every integral has its
 // own slot.)
+// The rank-th depth-kSplitLog2 node counted from node jp outwards, alternately above and below it
+// (jp, jp - 1, jp + 1, jp - 2, ...) until one side runs out; then the other side's remaining nodes
+// in turn, which are simply node `rank` (nothing left below) or kSplit - 1 - rank (nothing left above).
+NDPP_HD int split_segment(int jp, int rank) {
+  const int both = 2 * (jp < kSplit - jp ? jp : kSplit - jp);    // ranks that still alternate
+  if (rank < both) return (rank & 1) ? jp - ((rank + 1) >> 1) : jp + (rank >> 1);
+  return (jp < kSplit - jp) ? rank : kSplit - 1 - rank;
+}
+// The depth from which the accepted leaves on the way down to segment `seg` are its own: it is the
+// left-most segment below an ancestor at depth a iff its low kSplitLog2 - a index bits are zero.
+NDPP_HD int split_own_from(int seg) {
+  const unsigned low = (unsigned)seg | (1u << kSplitLog2);        // (segment 0: every ancestor)
+  return kSplitLog2 - highest_bit(low & (0u - low));
+}
+
+// work item `rank` of inner integral i
+template <int R, int LMAX>
+NDPP_HD void mu_init_split(const FgBatch& B, int i, int rank, MuLane<R, LMAX>& s) {
+  mu_init<R, LMAX>(B, i, s);
+  const int cur = split_segment(s.mask != 0 ? B.iti(kItemJp, i) : 0, rank);
+  s.path_left = kSplitLog2;
+  s.path_bits = (unsigned)cur;
+  s.slot_path = 0;
+  s.own_from = split_own_from(cur);
+  s.own_pending = (s.own_from != 0);
+}
+
+// Without a level's records -- the host simulator walks task after task --: the record of the one task
+// is built where the caller stands and read back by the very functions above, so a lane is set up
+// from a record here too.  t is a task of the level (mu_init) or one of its nt * kSplit work items,
+// item t / nt of integral t % nt (mu_init_split), as the device's wave loop hands them out.
+template <int R, int LMAX>
+NDPP_HD void mu_init(const FgBatch& B, int level, int base, int t, MuLane<R, LMAX>& s) {
+  double d[kItemDoubles];
+  int w[kItemInts];
+  FgBatch one = B;
+  one.it_d = d; one.it_i = w; one.icap = 1;
+  fg_item_build<R>(one, level, base, t, 0);
+  mu_init<R, LMAX>(one, 0, s);
+  s.task = t;
+}
 template <int R, int LMAX>
 NDPP_HD void mu_init_split(const FgBatch& B, int level, int base, int t, MuLane<R, LMAX>& s) {
   const int nt = B.n_mu_tasks(level);
   const int i = t % nt, rank = t / nt;
-  mu_init<R, LMAX>(B, level, base, i, s);
-  int jp = 0;
-  if (s.mask != 0) {
-#if NDPP_FAST
-    const double pa = s.q.p, qa = s.q.q;
-#else
-    const double pa = s.q.EpE / s.q.AkT, qa = 2.0 * s.q.s2 / s.q.AkT;
-#endif
-    const double x = ((pa - fabs(s.q.beta)) / qa - s.a) / (s.b - s.a) * (double)kSplit;
-    jp = (x > 0.0) ? (x < (double)(kSplit - 1) ? (int)x : kSplit - 1) : 0;   // (NaN: 0)
-  }
-  // the rank-th node counted from the peak outwards
-  int lo = jp - 1, hi = jp, cur = hi;
-  for (int k = 0; k <= rank; ++k) {
-    if (((k & 1) == 0 && hi < kSplit) || lo < 0) cur = hi++;
-    else cur = lo--;
-  }
-  s.path_left = kSplitLog2;
-  s.path_bits = (unsigned)cur;
-  s.slot_path = 0;
-  // the item is the left-most one below an ancestor at depth a iff its low kSplitLog2 - a index
-  // bits are zero
-  int tz = 0;
-  while (tz < kSplitLog2 && !(((unsigned)cur >> tz) & 1u)) ++tz;
-  s.own_from = kSplitLog2 - tz;
-  s.own_pending = (s.own_from != 0);
+  double d[kItemDoubles];
+  int w[kItemInts];
+  FgBatch one = B;
+  one.it_d = d; one.it_i = w; one.icap = 1;
+  fg_item_build<R>(one, level, base, i, 0);
+  mu_init_split<R, LMAX>(one, 0, rank, s);
+  s.task = i;
 }
 
 // split mode: F = ((0 + seg_0) + seg_1) + ... of every integral of the level

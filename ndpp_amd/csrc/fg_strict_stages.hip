@@ -44,6 +44,9 @@ int launch_fg_setup_strict(const void* batch, size_t batch_bytes, hipStream_t s)
 int launch_fg_prep_strict(const void* batch, size_t batch_bytes, int level, hipStream_t s) {
   return strict_stage(batch, batch_bytes, [&](const FgBatch& B) { launch_fg_prep(B, level, s); });
 }
+int launch_fg_item_strict(const void* batch, size_t batch_bytes, int level, hipStream_t s) {
+  return strict_stage(batch, batch_bytes, [&](const FgBatch& B) { launch_fg_item(B, level, s); });
+}
 int launch_fg_seg_zero_strict(const void* batch, size_t batch_bytes, int level, hipStream_t s) {
   return strict_stage(batch, batch_bytes, [&](const FgBatch& B) { launch_fg_seg_zero(B, level, s); });
 }
@@ -70,9 +73,9 @@ int launch_fg_assemble_strict(const void* batch, size_t batch_bytes, hipStream_t
 // (a table local to a host function, of plain functions: hipcc would emit a namespace-scope table, and
 // lambdas in its initialiser, for the device too)
 const FgStages& fg_strict_stages() {
-  static const FgStages table = {launch_fg_setup_strict,  launch_fg_prep_strict,    launch_fg_seg_zero_strict,
-                                 launch_fg_mu_strict,     launch_fg_combine_strict, launch_fg_node_strict,
-                                 launch_fg_reduce_strict, launch_fg_assemble_strict};
+  static const FgStages table = {launch_fg_setup_strict,    launch_fg_prep_strict,  launch_fg_item_strict,
+                                 launch_fg_seg_zero_strict, launch_fg_mu_strict,    launch_fg_combine_strict,
+                                 launch_fg_node_strict,     launch_fg_reduce_strict, launch_fg_assemble_strict};
   return table;
 }
 

@@ -100,6 +100,7 @@ void launch_file4_any(int n, const int* list, int mu_bins, const double* ein,
 struct FgStages {
   int (*setup)(const void* batch, size_t bytes, hipStream_t s);
   int (*prep)(const void* batch, size_t bytes, int level, hipStream_t s);
+  int (*item)(const void* batch, size_t bytes, int level, hipStream_t s);
   int (*seg_zero)(const void* batch, size_t bytes, int level, hipStream_t s);
   int (*mu)(const void* batch, size_t bytes, int level, int num_cu, double* gstack, int* counter, hipStream_t s);
   int (*combine)(const void* batch, size_t bytes, int level, hipStream_t s);

@@ -484,7 +484,8 @@ size_t bytes_per_node(int nch) {
   return sizeof(double) * (2 + 6 * (size_t)nch) + 4 * sizeof(int)  // node arrays
          + 2 * 8 * sizeof(double)                                   // 2 tasks: limits + 3 K per row
          + 2                                                        // 2 tasks: Gauss-rule flag
-         + sizeof(int);                                             // task order
+         + kItemDoublesStrict * sizeof(double) + kItemInts * sizeof(int)   // an item record (FgBatch::icap)
+         + sizeof(int);                                           // task order
 }
 
 // mixed-nuclide batch (ndpp_elastic_leg_multi): device arrays, per nuclide and per E_in
@@ -666,7 +667,9 @@ int plan_batch(const ndpp_params* p, int n_ein, int n_rows, int G, int rows_per_
              sizeof(int) * ((size_t)1 << L) + pl.contexts * pl.ctx_fixed + 4096;
   const size_t node_bytes = bytes_per_node(pl.nch);
   // job records + raw row + the level-0 alias table (FgBatch::t_alias: 5 records for each of a job's 5 G roots)
-  const size_t per_job_bytes = sizeof(double) * (GL + 3) + sizeof(int) * 2 + 16 + sizeof(int) * 25 * (size_t)G;
+  // (+ the item records of level 0, 25 G per job, where those outnumber the arena's nodes: FgBatch::icap)
+  const size_t per_job_bytes = sizeof(double) * (GL + 3) + sizeof(int) * 2 + 16 + sizeof(int) * 25 * (size_t)G +
+                               (kItemDoublesStrict * sizeof(double) + kItemInts * sizeof(int)) * 25 * (size_t)G;
   // What the whole batch would take in one chunk.  If the cached workspace already holds that,
   // the free-memory query (~0.1 ms; thousands of small calls in a library-shaped run) is skipped.
   const size_t whole = pl.fixed + ((size_t)n_ein + pl.contexts * pl.spare_ein) * pl.nodes_per_ein * node_bytes +
@@ -805,9 +808,10 @@ int classify_batch(const BatchCall& a, const FgTunables& t, bool look_at_tables,
 // library the strict one again.  (Internal linkage keeps these lambdas out of the device code; the exported
 // strict table needs plain functions for that: fg_strict_stages.hip.)
 inline const FgBatch& own(const void* batch) { return *static_cast<const FgBatch*>(batch); }
-const FgStages kFgOwnStages = {   // setup, prep, seg_zero, mu, combine, node, reduce, assemble
+const FgStages kFgOwnStages = {   // setup, prep, item, seg_zero, mu, combine, node, reduce, assemble
     [](const void* b, size_t, hipStream_t s) { launch_fg_setup(own(b), s); return 0; },
     [](const void* b, size_t, int level, hipStream_t s) { launch_fg_prep(own(b), level, s); return 0; },
+    [](const void* b, size_t, int level, hipStream_t s) { launch_fg_item(own(b), level, s); return 0; },
     [](const void* b, size_t, int level, hipStream_t s) { launch_fg_seg_zero(own(b), level, s); return 0; },
     [](const void* b, size_t, int level, int num_cu, double* gstack, int* counter, hipStream_t s) {
       launch_mu_any(own(b), level, num_cu, gstack, counter, s); return 0; },
@@ -915,6 +919,13 @@ int carve_contexts(std::vector<FgCtx>& ctx, bool side_by_side, const BatchCall& 
     B.tcap = 2 * B.ncap;
     B.t_mulo = cv.take<double>(B.tcap); B.t_muhi = cv.take<double>(B.tcap);
     B.t_X = cv.take<double>((size_t)3 * (pl.joint ? 2 : 1) * B.tcap);
+    // The item records of a level (fg_item_build), rebuilt per level after its sort: room for one per node
+    // of the arena, and for level 0 of the largest chunk (5 per root).  A level's inner integrals are two
+    // per node of the LEVEL, so only a level that holds more than half of the arena's nodes does not fit; it
+    // raises the overflow flag and the chunk is redone with half the energies, as when the arena runs out.
+    B.icap = (int)std::min<long>(B.tcap, std::max<long>(B.ncap, 5L * kSegPerGroup * a.G * max_jobs));
+    B.it_d = cv.take<double>((size_t)((c.strict || !NDPP_FAST) ? kItemDoublesStrict : kItemDoublesFast) * B.icap);
+    B.it_i = cv.take<int>((size_t)kItemInts * B.icap);
     // the Gauss rule for the inner integrals the reference has converged: product-arithmetic
     // contexts only, and only when the batch's tables were looked at (a context of the product
     // arithmetic then holds energies of rows linear in mu only)
@@ -1023,7 +1034,7 @@ int enqueue_chunk(FgCtx& c, const BatchCall& a, const FgTunables& t, const Batch
     c.this_ein = std::min<long>(c.chunk_ein, c.n - c.done);
     B.n_jobs = pl.joint ? (int)c.this_ein : (int)(c.this_ein * rows_per_ein);
     const int ntrees = B.n_trees();
-    if ((long)ntrees * kSegPerGroup <= (long)B.tcap && ntrees <= B.ncap) break;
+    if ((long)ntrees * kSegPerGroup <= (long)B.icap && ntrees <= B.ncap) break;
     // more roots than the arena can even start with: take fewer energies
     if (c.chunk_ein <= 1) return fail(NDPP_EOVERFLOW, "arena of %d nodes is too small for one E_in", B.ncap);
     c.chunk_ein = std::max<long>(1, c.chunk_ein / 2);
@@ -1061,6 +1072,7 @@ int enqueue_chunk(FgCtx& c, const BatchCall& a, const FgTunables& t, const Batch
       hipLaunchKernelGGL(fg_sort_scatter_kernel, dim3(1024), dim3(256), 0, s, B, level, pl.nb_sort,
                          c.sl.mask_hist, c.order);
     }
+    if (int rc = st.item(&B, sizeof B, level, s)) return rc;
     if (B.seg)
       if (int rc = st.seg_zero(&B, sizeof B, level, s)) return rc;
     c.walk_ev.emplace_back();
