@@ -20,7 +20,8 @@ from .lib import (_check, Params, Stats, NdppError, load, library_path, mu_grid,
                   SCATT_LEGENDRE, SCATT_TABULAR, MAX_TAB_BINS, elastic_tab_batch, file6_tab_batch,
                   law9_tab_batch, sab_tab_batch, scatt_nuclide_tab, scatt_library_tab, scatt_library_at, grid_error,
                   thin_segments, thin_bounded, lib_compare,
-                  scatt_sample, sample_brackets, SAMPLE_OK, SAMPLE_SKIPPED, SAMPLE_BADROW, SAMPLE_ZEROROW, SAMPLE_NEGDENSITY)
+                  scatt_sample, sample_brackets, SAMPLE_OK, SAMPLE_SKIPPED, SAMPLE_BADROW, SAMPLE_ZEROROW, SAMPLE_NEGDENSITY,
+                  scatt_score, scatt_score_info, SCORE_OK, SCORE_SKIPPED, SCORE_BADROW, SCORE_ZEROROW)
 from .scatt import binary_search, elastic_brackets, calc_elastic_grid  # noqa: F401
 
 __version__ = "0.2.0"

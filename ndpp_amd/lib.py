@@ -30,6 +30,11 @@ NDPP_MAX_ORDER = 11
 NDPP_MAX_TAB_BINS = 128
 # per-event status of ndpp_scatt_sample
 SAMPLE_OK, SAMPLE_SKIPPED, SAMPLE_BADROW, SAMPLE_ZEROROW, SAMPLE_NEGDENSITY = 0, 1, 2, 3, 4
+# per-event status of ndpp_scatt_score, its chunk length, and the names of ndpp_scatt_score_info's figures
+SCORE_OK, SCORE_SKIPPED, SCORE_BADROW, SCORE_ZEROROW = 0, 1, 2, 3
+NDPP_SCORE_CHUNK = 256
+SCORE_INFO = ["bracket_ms", "factor_ms", "group_ms", "upload_ms", "kernel_ms", "download_ms", "passes", "scored",
+              "chunks"]
 
 EXPORTS = [
     "ndpp_default_params", "ndpp_version", "ndpp_last_error", "ndpp_last_gpu_ms",
@@ -51,7 +56,7 @@ EXPORTS = [
     "ndpp_scatt_library_tab", "ndpp_sab_tab_batch", "ndpp_scatt_library_at", "ndpp_grid_error",
     "ndpp_thin_segments", "ndpp_thin_bounded", "ndpp_lib_compare",
     "ndpp_scatt_minimum", "ndpp_scatt_minimum_evals", "ndpp_scatt_repair", "ndpp_scatt_repair_evals",
-    "ndpp_scatt_sample", "ndpp_sample_brackets",
+    "ndpp_scatt_sample", "ndpp_sample_brackets", "ndpp_scatt_score", "ndpp_scatt_score_info",
 ]
 
 
@@ -645,6 +650,10 @@ def load(build_if_missing: bool = False, torch_compat: bool | None = None) -> C.
                                           c_double_p, c_double_p, c_double_p, c_int_p, c_double_p, c_int_p]
         lib.ndpp_sample_brackets.argtypes = [C.c_int, c_double_p, C.c_long, c_double_p, c_double_p, c_double_p,
                                              c_int_p, c_double_p]
+        lib.ndpp_scatt_score.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_double_p, c_double_p, C.c_long,
+                                         c_double_p, c_double_p, c_int_p, C.c_int, c_double_p, c_double_p,
+                                         C.POINTER(C.c_long), c_int_p]
+        lib.ndpp_scatt_score_info.argtypes = [c_double_p, C.c_int]
     _lib = lib
     return lib
 
@@ -1082,6 +1091,38 @@ def sample_brackets(x, ein, u_g, u_mu):
     row, weight = np.zeros(max(n_ev, 1), dtype=np.int32), np.zeros(max(n_ev, 1))
     _check(load().ndpp_sample_brackets(len(x), _dp(x), n_ev, _dp(ein), _dp(u_g), _dp(u_mu), _ip(row), _dp(weight)))
     return row[:n_ev], weight[:n_ev]
+
+
+def scatt_score(normalize, scatt_type, x, y, ein, weight, bin, n_bins):
+    """ndpp_scatt_score: the events (ein, weight, bin) scored into n_bins tallies of the section x[n],
+    y[n][G][L] read linearly in ln E (include/ndpp_hip.h): every event adds v times its whole blended
+    row to tally[bin], v = weight (normalize 0) or weight / W (normalize 1, W the row's total mass by
+    scatt_type's rule), in the fixed chunked order.  Returns (tally[n_bins][G][L], wsum[n_bins],
+    count[n_bins] int64, status[n_ev] int32); status is one of SCORE_OK, SCORE_SKIPPED, SCORE_BADROW,
+    SCORE_ZEROROW."""
+    x, y = _f64(x), _f64(y)
+    ein, weight, bin = _f64(ein).ravel(), _f64(weight).ravel(), _i32(bin).ravel()
+    if y.ndim != 3 or x.shape != (y.shape[0],):
+        raise ValueError(f"x must be (n,) and y (n, G, L), got {x.shape} and {y.shape}")
+    if not (len(ein) == len(weight) == len(bin)):
+        raise ValueError(f"ein, weight and bin must have one length, got {len(ein)}, {len(weight)}, {len(bin)}")
+    n, G, L = y.shape
+    n_ev, n_bins = len(ein), int(n_bins)
+    tally, wsum = np.zeros((max(n_bins, 1), G, L)), np.zeros(max(n_bins, 1))
+    count = np.zeros(max(n_bins, 1), dtype=np.int64)
+    status = np.zeros(max(n_ev, 1), dtype=np.int32)
+    _check(load().ndpp_scatt_score(int(normalize), int(scatt_type), G, L, n, _dp(x), _dp(y), n_ev, _dp(ein),
+                                   _dp(weight), _ip(bin), n_bins, _dp(tally), _dp(wsum),
+                                   count.ctypes.data_as(C.POINTER(C.c_long)), _ip(status)))
+    return tally, wsum, count, status[:n_ev]
+
+
+def scatt_score_info() -> dict:
+    """ndpp_scatt_score_info: host and device times (ms), passes, scored events and chunks of this thread's
+    last scatt_score"""
+    out = np.zeros(len(SCORE_INFO))
+    _check(load().ndpp_scatt_score_info(_dp(out), len(out)))
+    return dict(zip(SCORE_INFO, (float(v) for v in out)))
 
 
 def _thin_args(x, y, y2, tokeep):
