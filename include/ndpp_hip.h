@@ -1047,6 +1047,66 @@ int ndpp_scatt_score(int normalize, int scatt_type, int G, int L,
  * test of the passes), not a stable part of the ABI: see the constants above.                       */
 int ndpp_scatt_score_info(double *out, int n);
 
+/* ---- ACE law 66: N-body phase space, in closed form -----------------------
+ * The reference leaves a reaction whose energy distribution is law 66 uninitialised
+ * (scattdata_header.F90:105-109): it adds nothing to a library.  ndpp_nbody_leg_batch integrates it.
+ * There is no table and nothing is interpolated in E_in: the density is closed-form at every
+ * incoming energy.
+ *   out[e][g][l], l < L = p->order: the moment of order l of group [lo, hi] = e_bins[g], e_bins[g+1]
+ *     at E = ein[e], fully written, not scaled by a cross section or p_valid (as ndpp_file6_leg_batch)
+ *   status[e]: NDPP_ST_RANGE and a zero row for an E that is not positive and finite (as the other
+ *     batch calls); NDPP_ST_NONFINITE as everywhere.  May be NULL.
+ * With A = awr, Q the reaction's Q value, n = n_bodies in 3..5 and Ap > 1 (the two LDAT words):
+ *   Emax = ((Ap - 1) / Ap) * ((A / (A + 1)) * E + Q),   E0 = E / ((A + 1) * (A + 1)).
+ * Emax <= 0: the row is zero.  In the centre of mass the neutron energy T has the density
+ * x^(1/2) (1 - x)^(3n/2 - 4) / B(3/2, 3n/2 - 3), x = T / Emax, the direction is isotropic, and the lab
+ * energy is E' = T + E0 + 2 muc sqrt(T E0).  A group that misses the lab window -- hi <= wl * wl or
+ * lo >= wh * wh, wl = max(sqrt(E0) - sqrt(Emax), 0), wh = sqrt(Emax) + sqrt(E0) -- is zero without
+ * integrating.  Otherwise, in IEEE double, one operation per written operator, no contraction, x[k]
+ * and w[k] (k = 0..31, ascending) the 32-point Gauss-Legendre rule of ndpp_nbody_rule:
+ *   rE0 = sqrt(E0), rlo = sqrt(lo), rhi = sqrt(hi)
+ *   breakpoints: for d in (rlo - rE0, rlo + rE0, rhi - rE0, rhi + rE0): Tb = d * d; kept when
+ *     0 < Tb < Emax, as sg / (1 + sqrt(1 - sg * sg)), sg = sqrt(Tb / Emax).  The kept values, 0 and 1,
+ *     sorted, equal values once: consecutive values pa < pb are the pieces, ascending.
+ *   outer node j of a piece:
+ *     hm = 0.5 * (pb - pa), cm = 0.5 * (pb + pa), t = cm + hm * x[j], wt = hm * w[j]
+ *     q = 1 + t * t, s = (2 * t) / q, c = (1 - t * t) / q, s2 = s * s, T = Emax * s2
+ *     c2 = c * c, c4 = c2 * c2, cp = c2 (n = 3), c4 * c (n = 4), c4 * c4 (n = 5)
+ *     W = ((K * s2) * cp) * (2 / q), K = 2 / B: 16/pi, 105/8, 512/(7 pi) rounded once
+ *     (T = Emax sin^2(theta), theta = 2 atan t: both end-point singularities are gone)
+ *     rT = sqrt(T), ia = max(|rT - rE0|, rlo), ib = min(rT + rE0, rhi); I_l = 0.0, and unless ib > ia
+ *     they stay so; else with hm2 = 0.5 * (ib - ia), cm2 = 0.5 * (ib + ia), den = (2 * rT) * rE0:
+ *   inner node k, in s' = sqrt(E'):
+ *     sp = cm2 + hm2 * x[k], fk = (hm2 * w[k]) * (sp / den)
+ *     mu = ((sp - rT) * (sp + rT)) / ((2 * sp) * rE0) + rE0 / (2 * sp), clamped to [-1, 1]
+ *     P_0 = 1, P_1 = mu, P_(l+1) = (((2l + 1) / (l + 1)) * mu) * P_l - (l / (l + 1)) * P_(l-1),
+ *     the quotients rounded once (the recurrence of ndpp_scatt_sample)
+ *     I_l = I_l + fk * P_l, k ascending
+ *   v_l[j] = (wt * W) * I_l;  piece_l = v_l[0] + ... + v_l[31], from 0.0, j ascending;
+ *   out[e][g][l] = the pieces, from 0.0, ascending.
+ * The cut at the breakpoints is what makes the rule converge: the inner limits have kinks in T where
+ * a group edge enters or leaves the kinematic window.  tests/nbody_ref.py restates the operations
+ * (nbody_numpy gives the same bits) and measures the rule against finer ones; the figures are in
+ * profiles/nbody/README.md.
+ * NDPP_EINVAL, decided before the device is touched: p NULL, its order or mu_bins out of range, G < 1,
+ * n_bodies outside 3..5, Ap not a finite number above 1, awr not finite and positive, Q not finite,
+ * n_ein < 0; for n_ein > 0 a NULL array, a G * L that does not fit an index.  n_ein == 0 is an empty
+ * success.  Without a device NDPP_EDEVICE.                                                          */
+int ndpp_nbody_leg_batch(const ndpp_params *p, double awr, double Q, int n_bodies, double Ap,
+                         int n_ein, const double *ein, int G, const double *e_bins,
+                         double *out /* [n_ein][G][L] */, int *status /* [n_ein] */);
+/* the nodes and weights the call uses (host only; for restatements) */
+void ndpp_nbody_rule(double x[32], double w[32]);
+/* Opt-in, process-wide, default 0; returns the previous value.  The whole-nuclide calls read it once
+ * per nuclide.  With 1, a law-66 energy distribution of a scattering reaction (is_valid_scatter) is a
+ * ScattData of its own: no angular distribution is fabricated for it, its grid is
+ * {max(threshold energy, e_bins[0]), top edge} (none when that is not below the top edge), and its
+ * rows come from ndpp_nbody_leg_batch, scaled and summed like any other reaction's.  A tabular call
+ * that meets such a reaction returns NDPP_EINVAL: law 66 has Legendre output only.  With 0 nothing
+ * changes anywhere.  ndpp_scattdata_shape and ndpp_convert_distro do not read it.                   */
+int ndpp_set_nbody(int enable);
+int ndpp_get_nbody(void);
+
 #ifdef __cplusplus
 }
 #endif

@@ -27,10 +27,11 @@ SOURCES = [(CSRC / "ndpp_hip.hip", False), (CSRC / "fg_strict_stages.hip", True)
            (CSRC / "tab_kernels.hip", True), (CSRC / "grid_kernels.hip", True),
            (CSRC / "thin_kernels.hip", True), (CSRC / "compare_kernels.hip", True),
            (CSRC / "minimum_kernels.hip", True), (CSRC / "repair_kernels.hip", True),
-           (CSRC / "sample_kernels.hip", True), (CSRC / "score_kernels.hip", True)]
+           (CSRC / "sample_kernels.hip", True), (CSRC / "score_kernels.hip", True),
+           (CSRC / "nbody_kernels.hip", True)]
 HEADERS = [CSRC / "ndpp_math.h", CSRC / "fg_pipeline.h", CSRC / "fg_device.h", CSRC / "kernels.h", CSRC / "dev_util.h",
            CSRC / "file6_device.h", CSRC / "section_util.h", CSRC / "minimum_row.h",
-           CSRC / "legendre_int.h", CSRC / "legendre_ref_forms.h", CSRC / "exp_tab.inc",
+           CSRC / "legendre_int.h", CSRC / "legendre_ref_forms.h", CSRC / "exp_tab.inc", CSRC / "nbody_rule.h",
            PKG.parent / "include" / "ndpp_hip.h"]
 
 # Product build: NDPP_FAST=1 (see ndpp_math.h) with FMA contraction.  The

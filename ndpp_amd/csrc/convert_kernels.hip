@@ -100,13 +100,6 @@ __global__ void convert_kernel(int ncol, MuGrid grid, const ColJob* jobs, const 
   }
 }
 
-// is_valid_scatter, scattdata_header.F90:1502-1515
-bool valid_scatter(int MT) {
-  if (MT == 2 || (MT >= 11 && MT <= 91))
-    return MT != 18 && MT != 19 && MT != 20 && MT != 21 && MT != 38;
-  return false;
-}
-
 // ScattData after init: which distributions it points at, its law and its grid
 struct Shape {
   bool is_init = false;

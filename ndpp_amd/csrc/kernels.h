@@ -34,6 +34,13 @@ int check_law9_edata(int n_edata, const double* edata);
 enum ParamChecks { kCheckOrder = 1, kCheckTab = 2, kCheckFreegas = 4 };
 int check_params(const ndpp_params* p, int G, int what, int n_tab = 0);
 
+// is_valid_scatter, scattdata_header.F90:1502-1515
+inline bool valid_scatter(int MT) {
+  if (MT == 2 || (MT >= 11 && MT <= 91))
+    return MT != 18 && MT != 19 && MT != 20 && MT != 21 && MT != 38;
+  return false;
+}
+
 // f(std::integral_constant<int, LMAX>) with the smallest LMAX of 4, 6, 8, 11 that holds L orders:
 // the kernels that keep their moments in registers are instantiated for these four
 template <class F>
@@ -138,6 +145,10 @@ int law9_batch_sink(const ndpp_params* p, int n_ein, const double* ein, const in
                     const double* w_hi, int n_rows, const double* f_tab, int n_edata,
                     const double* edata, int G, const double* e_bins, int n_tab, double* out, int* status,
                     DeviceSink* sink);
+// nbody_kernels.hip: ndpp_nbody_leg_batch with a sink (Legendre moments only)
+int nbody_batch_sink(const ndpp_params* p, double awr, double Q, int n_bodies, double Ap, int n_ein,
+                     const double* ein, int G, const double* e_bins, double* out, int* status,
+                     DeviceSink* sink);
 // tab_kernels.hip: law9_batch_sink's integrating kernel for n_tab = N > 0 (raw [n_ein][2][G][N], null
 // stream), and the tabular counterpart of elastic_leg_batch_sink
 void launch_law9_tab(int n_ein, const double* ein, const int* row_lo, int mu_bins, const double* f_tab,

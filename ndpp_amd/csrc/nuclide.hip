@@ -2,13 +2,13 @@
 // behind the C ABI, for hosts that are not the reference's Fortran.  scatt_nuclide_impl is the
 // sequence of its steps:
 //
-//   read_hooks              the NDPP_HIP_* hooks of this file, once per call
+//   read_hooks              the NDPP_HIP_* hooks of this file and ndpp_get_nbody, once per call
 //   convert_reactions       ScattData%init + convert_distro -> ndpp_scattdata_shape / ndpp_convert_distro
 //   cutoff_and_threshold    scatt.F90:103-123
 //   make_grids              create_Ein_grid -> ndpp_create_ein_grid (or the caller's lists); the result
 //   run_grid, per grid      calc_elastic_grid (:603-675) / calc_inelastic_grid (:682-778):
 //     select_energies, select_yields   the bookkeeping of one reaction
-//     integrate_reaction               integrate_distro's dispatch over the batch calls
+//     integrate_reaction               integrate_distro's dispatch over the batch calls (+ law 66, opt-in)
 //     ElasticAssign / HostSum / DeviceSum   take() a reaction's moments, finish() the grid
 //     copy_top_rows
 // "Bookkeeping" is scatt_interp_distro (scattdata_header.F90:391-499): threshold and
@@ -257,6 +257,7 @@ struct Call {
   int n_bins;
   const double* e_bins;
   int n_tab, G, L, M;     // n_tab = 0: L = p->order Legendre moments; n_tab > 0: L = n_tab bins
+  bool nbody;             // ndpp_set_nbody, read once per call: law 66 is integrated
   size_t GL;
   double Etop;
   Hooks hooks;
@@ -264,7 +265,7 @@ struct Call {
   Call(const ndpp_params* p_, const ndpp_ace_nuclide* nuc_, int n_bins_, const double* e_bins_, int n_tab_)
       : p(p_), nuc(nuc_), n_bins(n_bins_), e_bins(e_bins_), n_tab(n_tab_), G(n_bins_ - 1),
         L(n_tab_ > 0 ? n_tab_ : p_->order), M(p_->mu_bins), GL((size_t)G * L), Etop(e_bins_[G]),
-        hooks(read_hooks()), hc(hooks.host_timing) {}
+        nbody(ndpp_get_nbody() != 0), hooks(read_hooks()), hc(hooks.host_timing) {}
 };
 
 // ---- init + convert_distro for every reaction and nested distribution (:59-106)
@@ -320,8 +321,10 @@ void after_init(const Call& c, const ndpp_ace_edist* ed, double threshold_energy
   sd->edist = sd->has_edist ? ed : nullptr;
 }
 
-// integrate_distro's dispatch (:533-656): 1 angular only, 2 file 6 in the CM, 3 law 9, 4 file 6 in the lab
+// integrate_distro's dispatch (:533-656): 1 angular only, 2 file 6 in the CM, 3 law 9, 4 file 6 in the lab;
+// 5, not the reference's: law 66 in closed form (init_nbody)
 int distro_kind(const SD& sd) {
+  if (sd.law == 66) return 5;
   if (sd.has_adist && !sd.has_edist) return 1;
   if (sd.in_cm) return 2;
   if (sd.has_adist && sd.law == 9) return 3;
@@ -348,6 +351,21 @@ int convert_table(const Call& c, const ndpp_ace_reaction& a, int NE, int tot, SD
                              sd->eout.data(), sd->pdf.data(), sd->cdf.data(), sd->intt.data(), sd->f.data());
 }
 
+// Law 66 with the option on: the ScattData the reference leaves uninitialised (:105-109), initialised
+// here.  There is no table: the grid is the two ends of the reaction's range, which the grid builder and
+// the row search read, and the reaction's angular distribution is left as it is.  Nothing above the top
+// group edge: not initialised.
+void init_nbody(const Call& c, const ndpp_ace_edist* ed, double threshold_energy, SD* sd) {
+  const double e_lo = (threshold_energy > c.e_bins[0]) ? threshold_energy : c.e_bins[0];
+  if (e_lo >= c.Etop) return;
+  sd->is_init = true;
+  sd->law = 66;
+  sd->has_edist = true;
+  sd->edist = ed;
+  sd->NE = 2;
+  sd->e_grid = {e_lo, c.Etop};
+}
+
 // every reaction's SD list; RxnState lives here, one per reaction
 int convert_reactions(const Call& c, std::vector<SD>* sds) {
   const ndpp_ace_nuclide* nuc = c.nuc;
@@ -368,7 +386,13 @@ int convert_reactions(const Call& c, std::vector<SD>* sds) {
       SD sd;
       sd.rxn = &rx;
       sd.is_init = is_init != 0;
-      if (sd.is_init) {
+      if (c.nbody && ed && ed->law == 66 && valid_scatter(rx.MT)) {
+        if (c.n_tab > 0)
+          return fail(NDPP_EINVAL, "MT %d: law 66 (N-body phase space) has Legendre output only", rx.MT);
+        if (ed->n_data < 2 || !ed->data)
+          return fail(NDPP_EINVAL, "MT %d: law 66 needs its 2 data words (the number of bodies and Ap)", rx.MT);
+        init_nbody(c, ed, a.threshold_energy, &sd);
+      } else if (sd.is_init) {
         sd.law = law;
         after_init(c, ed, a.threshold_energy, &sd, &st);
         rc = convert_table(c, a, NE, tot, &sd);
@@ -524,6 +548,9 @@ int integrate_reaction(const Call& c, const SD& sd, int kind, double cutoff, con
                        DeviceSink* sink) {
   const ndpp_ace_nuclide* nuc = c.nuc;
   std::vector<int> status(s.nb);
+  if (kind == 5)
+    return nbody_batch_sink(c.p, nuc->awr, sd.rxn->Q_value, (int)sd.edist->data[0], sd.edist->data[1], s.nb,
+                            s.ein.data(), c.G, c.e_bins, res, status.data(), sink);
   if (kind == 1 && c.n_tab > 0)
     return elastic_tab_batch_sink(c.p, nuc->awr, nuc->kT, cutoff, sd.rxn->Q_value, s.nb, s.ein.data(),
                                   s.row_lo.data(), s.w_hi.data(), sd.NE, sd.f.data(), c.G, c.e_bins, c.n_tab, res,

@@ -57,6 +57,7 @@ EXPORTS = [
     "ndpp_thin_segments", "ndpp_thin_bounded", "ndpp_lib_compare",
     "ndpp_scatt_minimum", "ndpp_scatt_minimum_evals", "ndpp_scatt_repair", "ndpp_scatt_repair_evals",
     "ndpp_scatt_sample", "ndpp_sample_brackets", "ndpp_scatt_score", "ndpp_scatt_score_info",
+    "ndpp_nbody_leg_batch", "ndpp_nbody_rule", "ndpp_set_nbody", "ndpp_get_nbody",
 ]
 
 
@@ -654,6 +655,13 @@ def load(build_if_missing: bool = False, torch_compat: bool | None = None) -> C.
                                          c_double_p, c_double_p, c_int_p, C.c_int, c_double_p, c_double_p,
                                          C.POINTER(C.c_long), c_int_p]
         lib.ndpp_scatt_score_info.argtypes = [c_double_p, C.c_int]
+        lib.ndpp_nbody_leg_batch.argtypes = [PP, C.c_double, C.c_double, C.c_int, C.c_double, C.c_int, c_double_p,
+                                             C.c_int, c_double_p, c_double_p, c_int_p]
+        lib.ndpp_nbody_rule.argtypes = [c_double_p, c_double_p]
+        lib.ndpp_nbody_rule.restype = None
+        lib.ndpp_set_nbody.argtypes = [C.c_int]
+        lib.ndpp_set_nbody.restype = C.c_int
+        lib.ndpp_get_nbody.restype = C.c_int
     _lib = lib
     return lib
 
@@ -836,6 +844,34 @@ def law9_leg_batch(params: Params, ein, row_lo, w_hi, f_tab, edata, e_bins):
     """ndpp_law9_leg_batch: law9_scatter_lab_leg on both bracketing rows + blend
     (scattdata_header.F90:605-638)."""
     return _law9_batch(params, None, ein, row_lo, w_hi, f_tab, edata, e_bins)
+
+
+def nbody_leg_batch(params: Params, awr, Q, n_bodies, Ap, ein, e_bins):
+    """ndpp_nbody_leg_batch: the moments of ACE law 66 (N-body phase space) in closed form, per
+    incoming energy and group.  Returns out[n_ein][G][L], status[n_ein]."""
+    ein, e_bins = _f64(ein), _f64(e_bins)
+    G = e_bins.shape[0] - 1
+    p, out, status = _batch_out(params, params.mu_bins, len(ein), G)
+    _check(load().ndpp_nbody_leg_batch(C.byref(p), float(awr), float(Q), int(n_bodies), float(Ap), len(ein), _dp(ein),
+                                       G, _dp(e_bins), _dp(out), _ip(status)))
+    return out, status
+
+
+def nbody_rule():
+    """The 32 nodes and weights ndpp_nbody_leg_batch integrates with."""
+    x, w = np.zeros(32), np.zeros(32)
+    load().ndpp_nbody_rule(_dp(x), _dp(w))
+    return x, w
+
+
+def set_nbody(enable: bool) -> bool:
+    """ndpp_set_nbody: whether the whole-nuclide calls integrate law 66 (process-wide, default off).
+    Returns the previous setting."""
+    return bool(load().ndpp_set_nbody(int(bool(enable))))
+
+
+def get_nbody() -> bool:
+    return bool(load().ndpp_get_nbody())
 
 
 SCATT_LEGENDRE, SCATT_TABULAR, MAX_TAB_BINS = 0, 1, 128

@@ -71,7 +71,15 @@ Positivity (ndpp_amd.repair; Legendre output only):
   --repair-steps N     bisection steps, 1..52 (default 20): t is within 2^-N of a failing value
   --repair-rel-tol X   the certificate's tolerance, finite and >= 0 (default 1e-10)
   --repair-undecided   also repair rows whose minimum is within the tolerance of zero
-                       Each of the four is an input error without --repair-positivity."""
+                       Each of the four is an input error without --repair-positivity.
+
+N-body phase space (ACE law 66; Legendre output only):
+  --nbody              integrate the reactions whose energy distribution is law 66 (deuterium's
+                       (n,2n) is the best-known one) in closed form (lib.set_nbody; DESIGN.md section
+                       20).  Without the flag they add nothing to the library, as in the reference.
+                       The option is set for the run's library calls and put back afterwards; how many
+                       reactions were integrated under law 66 goes under "nbody" in --json.  A tabular
+                       run whose tables carry law 66 is an input error."""
 from __future__ import annotations
 
 import argparse
@@ -414,6 +422,27 @@ def compute(s: dict, tables: list, grid_opts: dict | None = None, repair_opts: d
     return out, recs, grid_rep
 
 
+def nbody_reactions(tables: list, bins) -> dict:
+    """Per neutron table that carries law 66: the number of reactions --nbody integrates under it (a
+    scattering MT, is_valid_scatter, whose threshold energy is below the top group edge)."""
+    out = {}
+    for t in tables:
+        if t["kind"] != "neutron":
+            continue
+        d, n, carries = t["data"], 0, False
+        for r in d["reactions"]:
+            if not any(int(ed["law"]) == 66 for ed in r["edists"]):
+                continue
+            carries = True
+            mt = int(r["MT"])
+            valid = mt == 2 or (11 <= mt <= 91 and mt not in ace.FISSION_MTS)
+            if valid and max(float(d["energy"][int(r["thr"]) - 1]), float(bins[0])) < float(bins[-1]):
+                n += 1
+        if carries:
+            out[t["listing"]["name"]] = n
+    return out
+
+
 def lib_xml_of(s: dict, run_dir, tables: list) -> bytes:
     rows = []
     for t in tables:
@@ -465,7 +494,7 @@ def write_library(run_dir, files: list, xml: bytes) -> list:
 
 
 def run(run_dir, json_path=None, out=sys.stdout, grid_opts: dict | None = None,
-        repair_opts: dict | None = None, thermal_tabular: bool = False) -> int:
+        repair_opts: dict | None = None, thermal_tabular: bool = False, nbody: bool = False) -> int:
     """The whole driver; returns the exit status."""
     run_dir = Path(run_dir)
     t_start = time.perf_counter()
@@ -486,6 +515,10 @@ def run(run_dir, json_path=None, out=sys.stdout, grid_opts: dict | None = None,
         tables = load_tables(s, xs)
         if not tables:
             raise InputError("no neutron or thermal tables to process")
+        law66 = nbody_reactions(tables, s["energy_bins"]) if nbody else {}
+        if law66 and s["scatt_type"] == "tabular":
+            raise InputError(f"--nbody: {', '.join(law66)} carries ACE law 66, which has Legendre output only: give "
+                             "it with <scatt_type> legendre")
     except InputError as e:
         print(f"ndpp_amd.run: input error: {e}", file=sys.stderr)
         return EXIT_INPUT
@@ -498,10 +531,15 @@ def run(run_dir, json_path=None, out=sys.stdout, grid_opts: dict | None = None,
             print(f"ndpp_amd.run: input error: {e}", file=sys.stderr)
             return EXIT_INPUT
         repair_rep = None
-        if repair_opts is not None:
-            files, recs, grid_rep, repair_rep = compute(s, tables, grid_opts, repair_opts)
-        else:
-            files, recs, grid_rep = compute(s, tables, grid_opts)
+        nbody_before = lib.set_nbody(True) if nbody else False
+        try:
+            if repair_opts is not None:
+                files, recs, grid_rep, repair_rep = compute(s, tables, grid_opts, repair_opts)
+            else:
+                files, recs, grid_rep = compute(s, tables, grid_opts)
+        finally:
+            if nbody:
+                lib.set_nbody(nbody_before)
         xml = lib_xml_of(s, run_dir, tables)
     except (lib.NdppError, RuntimeError, OSError) as e:
         print(f"ndpp_amd.run: library error: {e}", file=sys.stderr)
@@ -536,6 +574,8 @@ def run(run_dir, json_path=None, out=sys.stdout, grid_opts: dict | None = None,
         rec = dict(run_dir=str(run_dir), wall_s=total, scatt_type=s["scatt_type"], tables=recs)
         if grid_opts is not None:
             rec["grid"] = grid_rep
+        if nbody:
+            rec["nbody"] = dict(reactions=sum(law66.values()), tables=law66)
         if repair_rep is not None:
             rec["repair"] = dict(repair_opts, tables=[dict(name=t["name"], kind=t["kind"], **t["report"].as_dict())
                                                       for t in repair_rep])
@@ -627,6 +667,9 @@ def main(argv=None) -> int:
     ap.add_argument("--thermal-tabular", action="store_true",
                     help="with scatt_type tabular: write the thermal S(alpha,beta) tables in bins too, every "
                          "discrete cosine's mass whole in its bin (without it such a run is refused)")
+    ap.add_argument("--nbody", action="store_true",
+                    help="integrate the reactions under ACE law 66 (N-body phase space) in closed form; without it "
+                         "they add nothing, as in the reference (Legendre output only)")
     a = ap.parse_args(argv)
     try:
         grid_opts = _grid_options(a)
@@ -634,7 +677,8 @@ def main(argv=None) -> int:
     except InputError as e:
         print(f"ndpp_amd.run: input error: {e}", file=sys.stderr)
         return EXIT_INPUT
-    return run(a.run_dir, a.json, grid_opts=grid_opts, repair_opts=repair_opts, thermal_tabular=a.thermal_tabular)
+    return run(a.run_dir, a.json, grid_opts=grid_opts, repair_opts=repair_opts, thermal_tabular=a.thermal_tabular,
+               nbody=a.nbody)
 
 
 if __name__ == "__main__":
