@@ -35,7 +35,7 @@ def mu_grid(M):
 def load_ref():
     R = C.CDLL(str(REF))
     R.ref_set_params.argtypes = [d, d, d, i, d, i, i, i, i, i]
-    R.ref_set_params(1e-6, 1e-6, 1e-7, 15, 1e-8, 15, 20, 10, 50, 30)
+    R.ref_set_params(*REF_PARAMS)
     R.ref_integrate_freegas_leg.argtypes = [d, d, d, P, P, i, P, i, i, P]
     R.ref_integrate_file4_cm_leg.argtypes = [P, d, d, d, P, i, P, i, i, P]
     R.ref_calc_pn.restype = d
@@ -159,37 +159,63 @@ SAB_CASES = [(0, None, 6, "g2"), (1, "incoherent", 6, "g2"), (2, None, 6, "g8"),
              (2, "coherent", 4, "g2"), (1, "coherent", 4, "g8")]
 
 
-def sab_goldens(R):
+def sab_marshal(t):
+    """The twenty table arguments that ref_calc_scattsab and ref_sab_egrid share, from a dict in the
+    layout of tests/synth.sab_table; `keep` holds the arrays they point into."""
+    pi = C.POINTER(i)
+    keep = [np.ascontiguousarray(t[k], dtype=np.float64)
+            for k in ("ei", "sig", "e_out", "mu", "ce_out", "cpdf", "cmu", "ee", "eP", "emu")]
+    keep.append(np.ascontiguousarray(t["cptr"], dtype=np.int32))
+    args = (t["threshold_inelastic"], t["threshold_elastic"], t["NEi"], t["NEo"], t["NMU"],
+            t["mode"], dp(keep[0]), dp(keep[1]), dp(keep[2]), dp(keep[3]),
+            keep[10].ctypes.data_as(pi), dp(keep[4]), dp(keep[5]), dp(keep[6]), t["el_mode"],
+            t["NEe"], t["NMUe"], dp(keep[7]), dp(keep[8]), dp(keep[9]))
+    return args, keep
+
+
+def ref_scattsab(R, t, ein, bins, L):
+    """calc_scattsab's Legendre path through the reference: el, inel, scatt_mat, each [NE][G][L]"""
+    pi = C.POINTER(i)
+    R.ref_calc_scattsab.argtypes = [d, d, i, i, i, i, P, P, P, P, pi, P, P, P, i, i, i, P, P, P,
+                                    P, i, P, i, i, P, P, P]
+    ein, bins = np.ascontiguousarray(ein, dtype=np.float64), np.ascontiguousarray(bins, dtype=np.float64)
+    G, NE = len(bins) - 1, len(ein)
+    args, keep = sab_marshal(t)
+    e, q, m = (np.zeros((NE, G, L)) for _ in range(3))
+    R.ref_calc_scattsab(*args, dp(ein), NE, dp(bins), G + 1, L - 1, dp(e), dp(q), dp(m))
+    del keep
+    return e, q, m
+
+
+def ref_sab_grid(R, t, bins, cap=20000):
+    """sab_egrid through the reference"""
+    pi = C.POINTER(i)
+    R.ref_sab_egrid.argtypes = [d, d, i, i, i, i, P, P, P, P, pi, P, P, P, i, i, i, P, P, P, P, i,
+                                P, i, pi]
+    bins = np.ascontiguousarray(bins, dtype=np.float64)
+    args, keep = sab_marshal(t)
+    grid = np.zeros(cap)
+    ng = C.c_int()
+    R.ref_sab_egrid(*args, dp(bins), len(bins), dp(grid), cap, C.byref(ng))
+    del keep
+    assert 0 < ng.value <= cap, (ng.value, cap)
+    return grid[:ng.value].copy()
+
+
+def sab_goldens(R, out=None):
     """calc_scattsab's Legendre path (integrate_sab_el/inel + combine_sab_grid) and
     sab_egrid through the reference, on the synthetic thermal tables of tests/synth.py."""
     sys.path.insert(0, str(HERE.parent))
     from synth import sab_ein_grid, sab_table
-    pi = C.POINTER(i)
-    R.ref_calc_scattsab.argtypes = [d, d, i, i, i, i, P, P, P, P, pi, P, P, P, i, i, i, P, P, P,
-                                    P, i, P, i, i, P, P, P]
-    R.ref_sab_egrid.argtypes = [d, d, i, i, i, i, P, P, P, P, pi, P, P, P, i, i, i, P, P, P, P, i,
-                                P, i, pi]
-    out = {}
+    res = {}
     for n, (mode, el, L, gname) in enumerate(SAB_CASES):
         bins = (np.array([0.0, 6.25e-7, 20.0]) if gname == "g2"
                 else np.concatenate([[0.0], np.logspace(-9, np.log10(20.0), 8)]))
         t = sab_table(mode, seed=1000 + mode, elastic=el)
         ein = sab_ein_grid(t)
-        G, NE = len(bins) - 1, len(ein)
-        f64 = lambda k: np.ascontiguousarray(t[k], dtype=np.float64)
-        keep = [f64(k) for k in ("ei", "sig", "e_out", "mu", "ce_out", "cpdf", "cmu", "ee", "eP", "emu")]
-        cp = np.ascontiguousarray(t["cptr"], dtype=np.int32)
-        args = (t["threshold_inelastic"], t["threshold_elastic"], t["NEi"], t["NEo"], t["NMU"],
-                t["mode"], dp(keep[0]), dp(keep[1]), dp(keep[2]), dp(keep[3]),
-                cp.ctypes.data_as(pi), dp(keep[4]), dp(keep[5]), dp(keep[6]), t["el_mode"],
-                t["NEe"], t["NMUe"], dp(keep[7]), dp(keep[8]), dp(keep[9]))
-        e, q, m = (np.zeros((NE, G, L)) for _ in range(3))
-        R.ref_calc_scattsab(*args, dp(ein), NE, dp(bins), G + 1, L - 1, dp(e), dp(q), dp(m))
-        grid = np.zeros(20000)
-        ng = C.c_int()
-        R.ref_sab_egrid(*args, dp(bins), G + 1, dp(grid), len(grid), C.byref(ng))
-        out.update({f"c{n}_ein": ein, f"c{n}_bins": bins, f"c{n}_el": e, f"c{n}_inel": q,
-                    f"c{n}_mat": m, f"c{n}_egrid": grid[:ng.value].copy()})
+        e, q, m = ref_scattsab(R, t, ein, bins, L)
+        res.update({f"c{n}_ein": ein, f"c{n}_bins": bins, f"c{n}_el": e, f"c{n}_inel": q,
+                    f"c{n}_mat": m, f"c{n}_egrid": ref_sab_grid(R, t, bins)})
     # apply_tol_scatt (scatt.F90:786-818) on one of the matrices and on a random one
     R.ref_apply_tol_scatt.argtypes = [i, i, i, P, d]
     rng = np.random.default_rng(8)
@@ -198,8 +224,40 @@ def sab_goldens(R):
     tol_in = np.ascontiguousarray(raw)
     tol_out = tol_in.copy()
     R.ref_apply_tol_scatt(4, 8, 30, dp(tol_out), 1e-8)
-    out.update(tol_in=tol_in, tol_out=tol_out)
-    np.savez_compressed(HERE / "sab.npz", **out)
+    res.update(tol_in=tol_in, tol_out=tol_out)
+    np.savez_compressed(out or HERE / "sab.npz", **res)
+
+
+REF_PARAMS = (1e-6, 1e-6, 1e-7, 15, 1e-8, 15, 20, 10, 50, 30)       # load_ref()'s ref_set_params
+
+
+def sab_edge_goldens(R, out=None):
+    """calc_scattsab's Legendre path through the reference on every case of tests/synth.sab_edge_cases:
+    <case>_ein, _bins, _el, _inel, _mat, and _egrid (sab_egrid at EXTEND_PTS = synth.SAB_EDGE_EXTEND_PTS)
+    where the case's structure spans 0 .. 20 MeV; apply_tol_scatt on synth.apply_tol_edge_inputs:
+    tol_<name>_in, tol_<name>_out."""
+    sys.path.insert(0, str(HERE.parent))
+    from synth import SAB_EDGE_EXTEND_PTS, SAB_EDGE_TOL, apply_tol_edge_inputs, sab_edge_cases
+    res = {}
+    for name, c in sab_edge_cases().items():
+        e, q, m = ref_scattsab(R, c["table"], c["ein"], c["bins"], c["L"])
+        res.update({f"{name}_ein": c["ein"], f"{name}_bins": c["bins"], f"{name}_el": e, f"{name}_inel": q,
+                    f"{name}_mat": m})
+        if c["egrid"]:
+            R.ref_set_params(*REF_PARAMS[:8], SAB_EDGE_EXTEND_PTS, REF_PARAMS[9])
+            try:
+                res[f"{name}_egrid"] = ref_sab_grid(R, c["table"], c["bins"])
+            finally:
+                R.ref_set_params(*REF_PARAMS)
+        print(f"sab_edges: {name}: {len(c['ein'])} incoming energies, G = {len(c['bins']) - 1}, L = {c['L']}, "
+              f"{int((m[:, :, 0].sum(axis=1) == 0).sum())} rows without mass, {int(np.isnan(m).sum())} NaN")
+    R.ref_apply_tol_scatt.argtypes = [i, i, i, P, d]
+    for name, data in apply_tol_edge_inputs().items():
+        n, G, L = data.shape
+        o = data.copy()
+        R.ref_apply_tol_scatt(L, G, n, dp(o), SAB_EDGE_TOL)
+        res.update({f"tol_{name}_in": data, f"tol_{name}_out": o})
+    np.savez_compressed(out or HERE / "sab_edges.npz", **res)
 
 
 def ref_chi_case(R, c, ncap=64, entry="ref_calc_chi_pv"):
@@ -813,6 +871,7 @@ def main():
     file4_edge_goldens(R)
     file6_goldens(R)
     sab_goldens(R)
+    sab_edge_goldens(R)
     chi_goldens(R)
     chi_edge_goldens(R)
 
@@ -852,6 +911,8 @@ if __name__ == "__main__":
         file4_edge_goldens(load_ref())
     elif len(sys.argv) > 1 and sys.argv[1] == "chi_edges":
         chi_edge_goldens(load_ref())
+    elif len(sys.argv) > 1 and sys.argv[1] == "sab_edges":
+        sab_edge_goldens(load_ref())
     elif len(sys.argv) > 1 and sys.argv[1] == "tunables":
         tunables_goldens(load_ref())
     else:

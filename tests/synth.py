@@ -495,6 +495,167 @@ def chi_edge_cases():
             "p_valid": _case_p_valid()}
 
 
+# ---- thermal tables at their edges (sab_edge_cases) --------------------------
+SAB_G8 = np.concatenate([[0.0], np.logspace(-9, np.log10(20.0), 8)])          # the 8 groups of make_golden.SAB_CASES
+SAB_TOP_INSIDE = np.array([0.0, 1e-9, 1e-8, 1e-7, 3e-7])
+SAB_BOTTOM_ABOVE = np.array([1e-8, 3e-8, 1e-7, 3e-7, 1e-6, 20.0])
+SAB_EDGE_EXTEND_PTS = 2            # EXTEND_PTS of the stored sab_egrid (the default 50 only repeats each interval's fill)
+SAB_EDGE_TOL = 1e-8
+SAB_MODE_SEEDS = {0: 2000, 1: 2001, 2: 2002}        # the three tables of orders_* and groups_*
+
+
+def _nbrs(v):
+    v = float(v)
+    return [float(np.nextafter(v, -np.inf)), v, float(np.nextafter(v, np.inf))]
+
+
+def _sab_small(mode, seed, elastic=None, NEo=9, NMU=4, NEo_range=(5, 9)):
+    """sab_table with 8 incoming energies; incoherent elastic data on 8 of its 12 energies (both ends kept)"""
+    t = sab_table(mode, seed, NEi=8, NEo=NEo, NMU=NMU, elastic=elastic, NEo_range=NEo_range)
+    if elastic == "incoherent":
+        keep = np.array([0, 2, 3, 5, 6, 8, 10, 11])
+        t.update(NEe=8, ee=t["ee"][keep], eP=t["eP"][keep], emu=t["emu"].reshape(12, -1)[keep].ravel())
+    return t
+
+
+def sab_groups_bins(G):
+    if G == 1:
+        return np.array([0.0, 20.0])
+    if G == 70:
+        return np.concatenate([[0.0], _geom(1e-11, 1.5076, 70, last=20.0)])    # as chi_edge_cases' 70 groups
+    e = np.logspace(-11, np.log10(20.0), G)
+    e[-1] = 20.0
+    return np.concatenate([[0.0], e])
+
+
+def sab_edge_cases():
+    """Ordered name -> case of the thermal Legendre path: `table` (the layout of sab_table), `bins`,
+    `ein` (its own, never sab_egrid's), `L` (orders, scatt_order + 1), `cond` (the condition it exists
+    for; a condition that asks for a table per mode or per kind of elastic data has one case per
+    table, named <cond>_m<mode> or <cond>_<kind>), `why`, and `egrid` (the structure spans 0 .. 20 MeV,
+    so the reference's sab_egrid runs on it).  No case makes the reference stop: every threshold is
+    the last energy of its table, so binary_search never sees a value outside its array."""
+    out = {}
+
+    def add(name, cond, t, bins, ein, L, why):
+        bins = np.asarray(bins, dtype=np.float64)
+        out[name] = dict(cond=cond, table=t, bins=bins, ein=np.unique(np.asarray(ein, dtype=np.float64)), L=L,
+                         why=why, egrid=bool(bins[0] == 0.0 and bins[-1] >= 19.99))
+
+    three = lambda: {m: _sab_small(m, SAB_MODE_SEEDS[m], "incoherent") for m in (0, 1, 2)}
+    for L in (1, 11):
+        for m, t in three().items():
+            add(f"orders_{L}_m{m}", f"orders_{L}", t, SAB_G8, sab_ein_grid(t, n=14), L,
+                f"order {L} of pn_rt (scatt_order {L - 1}) on 8 groups, incoherent elastic data")
+    for G in (1, 70, 300):
+        for m, t in three().items():
+            add(f"groups_{G}_m{m}", f"groups_{G}", t, sab_groups_bins(G), sab_ein_grid(t, n=12), 2,
+                f"G = {G}" + (": every live row has P0 = 1" if G == 1 else
+                              ", log-spaced: rows whose plain sum of P0 over groups is not the compensated one"))
+
+    t = _sab_small(2, 2101)
+    ce, ptr = t["ce_out"].copy(), t["cptr"]
+    for k in (1, 3, 4, 6):
+        ce[ptr[k]] = 0.5 * ce[ptr[k] + 1]
+    t["ce_out"] = ce
+    first = min(ce[ptr[k]] for k in (1, 3, 4, 6))
+    add("cont_first_eout_positive", "cont_first_eout_positive", t,
+        np.unique([0.0, 0.25 * first, 0.75 * first, 1e-8, 1e-7, 1e-6, 20.0]), sab_ein_grid(t, n=12), 4,
+        "continuous rows whose first E_out is positive with three group edges below it: e_bins(g) < Eout(1) with "
+        "e_bins(g+1) < Eout(1) (the group is empty) and with e_bins(g+1) inside the row")
+
+    t = _sab_small(2, 2102)
+    ce, ptr = t["ce_out"].copy(), t["cptr"]
+    ce[ptr[2]] = 0.5 * ce[ptr[2] + 1]
+    t["ce_out"] = ce
+    add("cont_edges_on_points", "cont_edges_on_points", t,
+        np.unique([0.0, ce[ptr[2]], ce[ptr[3] + 2], ce[ptr[6] + 3], ce[ptr[6] - 1], 20.0]), sab_ein_grid(t, n=12), 4,
+        "interior group edges equal to the first point of row 2, to interior points of rows 3 and 6 (f = 0) and to "
+        "the last point of row 5 (the >= branches)")
+
+    t = _sab_small(2, 2104, NMU=1, NEo_range=(2, 4))
+    add("cont_two_point_rows", "cont_two_point_rows", t, SAB_G8, sab_ein_grid(t, n=12), 4,
+        "continuous rows of exactly two outgoing energies, one cosine each")
+
+    t = _sab_small(1, 2105, NEo=5, NMU=1)
+    add("skewed_min", "skewed_min", t, SAB_G8, sab_ein_grid(t, n=12), 4,
+        "the smallest legal skewed table: 5 outgoing energies (weights 0.1 0.4 1 0.4 0.1), one cosine")
+
+    for m in (0, 1, 2):
+        t = _sab_small(m, 2110 + m, "coherent")
+        top = SAB_TOP_INSIDE[-1]
+        add(f"top_inside_m{m}", "top_inside", t, SAB_TOP_INSIDE, np.concatenate([sab_ein_grid(t, n=12), _nbrs(top)]), 4,
+            "the top edge 3e-7 lies below both thresholds: discrete E_out at or past it, E_in on it and one ulp to "
+            "each side, rows left with no mass")
+        lo = SAB_BOTTOM_ABOVE[0]
+        add(f"bottom_above_zero_m{m}", "bottom_above_zero", t, SAB_BOTTOM_ABOVE,
+            np.concatenate([sab_ein_grid(t, n=12), _nbrs(lo)]), 4,
+            "the bottom edge 1e-8 lies above some discrete E_out and above some incoming energies")
+
+    for kind, m, seed in (("coherent", 0, 2120), ("incoherent", 2, 2121)):
+        t = _sab_small(m, seed, kind)
+        ee = t["ee"]
+        add(f"elastic_edges_{kind}", "elastic_edges", t, SAB_G8,
+            np.concatenate([np.concatenate([_nbrs(e) for e in ee]), [0.5 * ee[0]]]), 4,
+            "E_in on every elastic table energy (Bragg edge) and one ulp to each side, the elastic threshold and "
+            "one ulp below it, a point below the first elastic energy")
+
+    for m in (0, 1, 2):
+        t = _sab_small(m, 2130 + m)
+        ei = t["ei"]
+        add(f"inel_edges_m{m}", "inel_edges", t, SAB_G8,
+            np.concatenate([np.concatenate([_nbrs(e) for e in ei]), [0.5 * ei[0], 0.25 * ei[0]]]), 4,
+            "E_in on every inelastic table energy and one ulp to each side, the inelastic threshold with both "
+            "neighbours, two points below the first table energy")
+
+    for name, m, seed, scale, between in (("thresholds_el_below", 0, 2140, 0.1, [6e-7, 1e-6, 2.5e-6]),
+                                          ("thresholds_el_above", 2, 2141, 5.0, [6e-6, 1e-5, 1.5e-5])):
+        t = _sab_small(m, seed, "coherent")
+        t["ee"] = t["ee"] * scale
+        t["threshold_elastic"] = float(t["ee"][-1])
+        add(name, name, t, SAB_G8, np.concatenate([sab_ein_grid(t, n=10), between, _nbrs(t["threshold_elastic"])]), 4,
+            "the elastic threshold lies " + ("below" if scale < 1 else "above") + " the inelastic one, incoming "
+            "energies between the two: rows with " + ("inelastic" if scale < 1 else "elastic") + " scattering only")
+
+    t = _sab_small(1, 2150, "incoherent")
+    t["el_mode"] = 4
+    add("exact_with_cosines", "exact_with_cosines", t, SAB_G8, sab_ein_grid(t, n=12), 4,
+        "elastic mode EXACT with n_elastic_mu > 0: the reference's `pass` branch, el = sig * 0")
+
+    t = _sab_small(0, 2160, "incoherent")
+    add("two_energies", "two_energies", t, SAB_G8, [1e-9, 3e-8], 4,
+        "two incoming energies: the last row of scatt_mat is the copy of the first")
+    return out
+
+
+def apply_tol_edge_inputs():
+    """name -> data[n][G][L] for apply_tol_scatt at tol = SAB_EDGE_TOL: (L, G, n) = (1, 1, 1), (11, 8, 129),
+    (2, 70, 40), (2, 300, 40).  A few live groups per row, P0 over twelve decades; from n > 1 on, row 1 is all
+    zero, every positive P0 of row 2 is below tol (the reference gives 0 * (orig / 0) = NaN), row 3 has a P0
+    equal to tol, row 4 a negative P0, row 5 a single value above tol and nothing else, row 6 a negative total."""
+    out = {}
+    for L, G, n in ((1, 1, 1), (11, 8, 129), (2, 70, 40), (2, 300, 40)):
+        rng = np.random.default_rng(9000 + G)
+        p0 = rng.uniform(0, 1, (n, G)) * 10.0 ** rng.integers(-12, 1, (n, G))
+        d = rng.uniform(-1, 1, (n, G, L)) * p0[:, :, None]
+        d[:, :, 0] = p0
+        d = d * (rng.uniform(size=(n, G)) < min(1.0, 4.0 / G))[:, :, None]
+        if n == 1:
+            d[0, 0, :] = 3e-9
+        else:
+            d[1] = 0.0
+            d[2] = 0.0
+            d[2, :3, :] = np.array([3e-9, 9.9e-9, 1e-12])[:, None]
+            d[3, 0, 0] = SAB_EDGE_TOL
+            d[4, 0, 0], d[4, 1, 0] = -0.25, 0.9
+            d[5] = 0.0
+            d[5, G - 1, :] = 0.7
+            d[6] = 0.0
+            d[6, 0, 0], d[6, 1, 0] = -0.5, 0.25
+        out[f"L{L}_G{G}_n{n}"] = np.ascontiguousarray(d)
+    return out
+
+
 # ---- raw ACE blocks for the ACE -> tabular conversion (convert_file4 / convert_file6) ----
 def _ang_table(rng, interp, npts, positive=False):
     """[JJ, NP, cosines(NP), pdf(NP), cdf(NP)] of one ACE tabular angular distribution."""
