@@ -233,10 +233,10 @@ __device__ void chi_integrate(const ndpp_chi_spectrum& s, double Ein, int G, con
   }
 }
 
-__device__ double chi_ksum(const double* x, int n) {  // flang SUM: Kahan
-  double s = 0.0, c = 0.0;
-  for (int i = 0; i < n; ++i) { const double y = x[i] - c, t = s + y; c = (t - s) - y; s = t; }
-  return s;
+__device__ double chi_ksum(const double* x, int n) {  // flang SUM
+  KahanSum sum;
+  for (int i = 0; i < n; ++i) sum.add(x[i]);
+  return sum.s;
 }
 
 struct ChiDev {

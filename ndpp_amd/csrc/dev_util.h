@@ -37,6 +37,17 @@ __host__ __device__ inline int bsearch1_clamped(const double* a, int n, double v
   return i < 1 ? 1 : i;
 }
 
+// The sum as flang's SUM intrinsic takes it: compensated (Kahan), term by term in storage order.
+// For host code and the units that are always built with -ffp-contract=off; s is the sum so far.
+struct KahanSum {
+  double s = 0.0, c = 0.0;
+  __host__ __device__ inline void add(double x) {
+    const double y = x - c, t = s + y;
+    c = (t - s) - y;
+    s = t;
+  }
+};
+
 // grid size for a grid-stride loop over n items
 inline int nblk(long n, int threads) {
   return (int)std::max<long>(1, std::min<long>((n + threads - 1) / threads, 1 << 20));

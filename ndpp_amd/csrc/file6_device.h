@@ -48,6 +48,26 @@ __device__ double tab1(const double* data, double x) {
   }
 }
 
+// law9_scatter_lab_leg (:1274-1306): whether anything is emitted at Ein (false: the group's row stays
+// zero), and pE, the fraction of the evaporation spectrum that falls into the group [eg, eg1].
+// T is tab1(edata, Ein), the nuclear temperature at Ein.
+// exp_glibc (ndpp_math.h), the reference's own exp: the differences of exponentials below
+// cancel, a last-bit error of exp shows up at 1e-11 in the group fractions
+__device__ inline bool law9_group(const double* edata, double T, double Ein, double eg, double eg1, double& pE) {
+  const int NR = (int)edata[0];
+  const int NE = (int)edata[1 + 2 * NR];
+  const double U = edata[2 + 2 * NR + 2 * NE];
+  const double x = (Ein - U) / T;
+  const double I = T * T * (1.0 - exp_glibc(-x) * (1.0 + x));
+  if (Ein - U <= 0.0) return false;
+  double Egp1 = eg1, Eg = eg;
+  if (Egp1 > (Ein - U)) Egp1 = Ein - U;
+  if (Eg > (Ein - U)) Eg = Ein - U;
+  pE = (exp_glibc(-Egp1 / T) * (T + Egp1)) - (exp_glibc(-Eg / T) * (T + Eg));
+  pE = -T * pE / I;
+  return true;
+}
+
 }  // namespace
 
 // (named, not internal: the tabular launchers of tab_kernels.hip take a batch from

@@ -159,19 +159,14 @@ __global__ __launch_bounds__(64) void f6_lab_panel_kernel(F6Batch B) {
   }
 }
 
-// Stage L3: thread per incoming energy: f_lo = ONE / sum(distro(1,:)) (:1447-1448).
-// flang's SUM intrinsic is Kahan-compensated; reproduced here.
+// Stage L3: thread per incoming energy: f_lo = ONE / sum(distro(1,:)) (:1447-1448), the sum
+// as flang's SUM intrinsic takes it.
 __global__ void f6_lab_norm_kernel(F6Batch B) {
   for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < B.n_ein; e += gridDim.x * blockDim.x) {
     double* o = B.out + (size_t)e * B.G * B.L;
-    double s = 0.0, c = 0.0;
-    for (int g = 0; g < B.G; ++g) {
-      const double y = o[(size_t)g * B.L] - c;
-      const double t = s + y;
-      c = (t - s) - y;
-      s = t;
-    }
-    const double f_lo = 1.0 / s;
+    KahanSum sum;
+    for (int g = 0; g < B.G; ++g) sum.add(o[(size_t)g * B.L]);
+    const double f_lo = 1.0 / sum.s;
     for (int k = 0; k < B.G * B.L; ++k) o[k] = o[k] * f_lo;
   }
 }
@@ -191,20 +186,8 @@ __global__ __launch_bounds__(64) void law9_kernel(int n_ein, const double* ein, 
     double acc[LMAX], pan[LMAX];
 #pragma unroll
     for (int l = 0; l < LMAX; ++l) acc[l] = 0.0;
-    const int NR = (int)edata[0];
-    const int NE = (int)edata[1 + 2 * NR];
-    const double T = tab1(edata, Ein);
-    const double U = edata[2 + 2 * NR + 2 * NE];
-    const double x = (Ein - U) / T;
-    // exp_glibc (ndpp_math.h), the reference's own exp: the differences of exponentials below
-    // cancel, a last-bit error of exp shows up at 1e-11 in the group fractions
-    const double I = T * T * (1.0 - exp_glibc(-x) * (1.0 + x));
-    if (!(Ein - U <= 0.0)) {
-      double Egp1 = e_bins[g + 1], Eg = e_bins[g];
-      if (Egp1 > (Ein - U)) Egp1 = Ein - U;
-      if (Eg > (Ein - U)) Eg = Ein - U;
-      double pE = (exp_glibc(-Egp1 / T) * (T + Egp1)) - (exp_glibc(-Eg / T) * (T + Eg));
-      pE = -T * pE / I;
+    double pE;
+    if (law9_group(edata, tab1(edata, Ein), Ein, e_bins[g], e_bins[g + 1], pE)) {
       LinearLegendre<LMAX> walk;
       walk.start(grid.at(0), fmu[0]);
       for (int imu = 1; imu <= grid.M - 1; ++imu) {

@@ -15,7 +15,7 @@
 // fixed order, so results repeat bit for bit.
 //
 // Built with -DNDPP_FAST=0 -ffp-contract=off like the Legendre integrators whose inputs and P0
-// these kernels share (file6_device.h, ndpp_math.h's strict arithmetic).
+// these kernels share (file4_device.h, file6_device.h, ndpp_math.h's strict arithmetic).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -26,6 +26,7 @@
 
 #include "../../include/ndpp_hip.h"
 #include "dev_util.h"
+#include "file4_device.h"
 #include "file6_device.h"
 #include "kernels.h"
 #include "ndpp_math.h"
@@ -151,13 +152,8 @@ __device__ __forceinline__ void f4_piece(double R, double xa, double xb, double 
   }
   f4_branch(R, xa, xb, fa, fb, (R < 1.0 && xb <= -R) ? -1.0 : 1.0, N, acc);
 }
-__device__ __forceinline__ double f4_f_at(const MuGrid& grid, const double* fw, double w, int iw) {
-  if (iw >= grid.M) return fw[grid.M - 1];
-  const double interp = (w - grid.at(iw - 1)) / (grid.at(iw) - grid.at(iw - 1));
-  return (1.0 - interp) * fw[iw - 1] + interp * fw[iw];
-}
 
-// integrate_file4_cm_leg's pieces (scattdata_header.F90:986-1076, file4_kernels.hip) with the
+// integrate_file4_cm_leg's pieces (scattdata_header.F90:986-1076, file4_device.h) with the
 // blended row (1 - fb) f_lo + fb f_hi, thread per (E_in of the list, group)
 __global__ __launch_bounds__(64) void f4_tab_kernel(int n, const int* list, MuGrid grid, const double* ein,
                                                     const int* row_lo, const double* w_hi,
@@ -170,21 +166,17 @@ __global__ __launch_bounds__(64) void f4_tab_kernel(int n, const int* list, MuGr
     double* row = out + ((size_t)i * G + g) * N;
     for (int k = 0; k < N; ++k) row[k] = 0.0;
     const double Ein = ein[i];
-    const double dw = grid.dmu_fgk;
-    const double R = awr * sqrt((1.0 + Q * (awr + 1.0) / (awr * Ein)));
-    const double onepawr2 = (1.0 + awr) * (1.0 + awr), onepR2 = 1.0 + R * R, inv2REin = 0.5 / (R * Ein);
-    double wlo = (e_bins[g] * onepawr2 - Ein * onepR2) * inv2REin;
-    wlo = wlo < -1.0 ? -1.0 : (wlo > 1.0 ? 1.0 : wlo);
-    double whi = (e_bins[g + 1] * onepawr2 - Ein * onepR2) * inv2REin;
-    whi = whi < -1.0 ? -1.0 : (whi > 1.0 ? 1.0 : whi);
-    if ((wlo == whi) && (wlo == -1.0 || wlo == 1.0)) continue;
-    const int ilo = (int)((wlo + 1.0) / dw) + 1, ihi = (int)((whi + 1.0) / dw) + 1;
+    const F4Kin kin = file4_kin(Ein, awr, Q);
+    const F4Bounds bd = file4_bounds(kin, Ein, grid.dmu_fgk, e_bins[g], e_bins[g + 1]);
+    if (bd.skip) continue;
+    const double R = kin.R, wlo = bd.wlo, whi = bd.whi;
+    const int ilo = bd.ilo, ihi = bd.ihi;
     const double* f0 = f_tab + (size_t)row_lo[i] * grid.M;
     const double* f1 = f0 + grid.M;
     const double fb = w_hi[i], fa = 1.0 - fb;
     auto fv = [&](int iw) { return fa * f0[iw] + fb * f1[iw]; };
-    const double flo = fa * f4_f_at(grid, f0, wlo, ilo) + fb * f4_f_at(grid, f1, wlo, ilo);
-    const double fhi = fa * f4_f_at(grid, f0, whi, ihi) + fb * f4_f_at(grid, f1, whi, ihi);
+    const double flo = fa * file4_f_at(grid, f0, wlo, ilo) + fb * file4_f_at(grid, f1, wlo, ilo);
+    const double fhi = fa * file4_f_at(grid, f0, whi, ihi) + fb * file4_f_at(grid, f1, whi, ihi);
     BinAcc acc(row);
     if (ilo != ihi) {
       f4_piece(R, wlo, grid.at(ilo), flo, fv(ilo), N, acc);
@@ -284,16 +276,13 @@ __global__ void f6_lab_tab_norm(F6Batch B) {
   const int N = B.L;
   for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < B.n_ein; e += gridDim.x * blockDim.x) {
     double* o = B.out + (size_t)e * B.G * N;
-    double s = 0.0, c = 0.0;
+    KahanSum sum;
     for (int g = 0; g < B.G; ++g) {
       double p0 = 0.0;
       for (int k = 0; k < N; ++k) p0 += o[(size_t)g * N + k];
-      const double y = p0 - c;
-      const double t = s + y;
-      c = (t - s) - y;
-      s = t;
+      sum.add(p0);
     }
-    const double f_lo = 1.0 / s;
+    const double f_lo = 1.0 / sum.s;
     for (int k = 0; k < B.G * N; ++k) o[k] = o[k] * f_lo;
   }
 }
@@ -311,18 +300,8 @@ __global__ __launch_bounds__(64) void law9_tab_kernel(int n_ein, const double* e
     for (int k = 0; k < N; ++k) row[k] = 0.0;
     const double Ein = ein[e];
     const double* fmu = f_tab + (size_t)(row_lo[e] + r) * grid.M;
-    const int NR = (int)edata[0];
-    const int NE = (int)edata[1 + 2 * NR];
-    const double T = tab1(edata, Ein);
-    const double U = edata[2 + 2 * NR + 2 * NE];
-    const double x = (Ein - U) / T;
-    const double I = T * T * (1.0 - exp_glibc(-x) * (1.0 + x));
-    if (Ein - U <= 0.0) continue;
-    double Egp1 = e_bins[g + 1], Eg = e_bins[g];
-    if (Egp1 > (Ein - U)) Egp1 = Ein - U;
-    if (Eg > (Ein - U)) Eg = Ein - U;
-    double pE = (exp_glibc(-Egp1 / T) * (T + Egp1)) - (exp_glibc(-Eg / T) * (T + Eg));
-    pE = -T * pE / I;
+    double pE;
+    if (!law9_group(edata, tab1(edata, Ein), Ein, e_bins[g], e_bins[g + 1], pE)) continue;
     BinAcc acc(row);
     double x0 = grid.at(0), y0 = fmu[0];
     for (int imu = 1; imu <= grid.M - 1; ++imu) {

@@ -103,13 +103,9 @@ std::string trimmed(const char* c) {
 // total (sums compensated like apply_tol_kernel's)
 void apply_tol_tab(int N, int G, int n, double* data, double tol) {
   auto total = [&](const double* d) {
-    double s = 0.0, c = 0.0;
-    for (int g = 0; g < G; ++g) {
-      const double y = group_p0(d + (size_t)g * N, N, true) - c, t = s + y;
-      c = (t - s) - y;
-      s = t;
-    }
-    return s;
+    KahanSum sum;
+    for (int g = 0; g < G; ++g) sum.add(group_p0(d + (size_t)g * N, N, true));
+    return sum.s;
   };
   for (int i = 0; i < n; ++i) {
     double* d = data + (size_t)i * G * N;

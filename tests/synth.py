@@ -625,7 +625,30 @@ def sab_edge_cases():
     t = _sab_small(0, 2160, "incoherent")
     add("two_energies", "two_energies", t, SAB_G8, [1e-9, 3e-8], 4,
         "two incoming energies: the last row of scatt_mat is the copy of the first")
+
+    for m in (0, 1):
+        t = sab_revisit_table(m)
+        ei = t["ei"]
+        grid = sab_ein_grid(t, n=20)
+        add(f"eout_revisits_group_m{m}", "eout_revisits_group", t, SAB_G8,
+            np.concatenate([grid[grid <= ei[4]], ei[:5], [ei[6]]]), 4,
+            "discrete E_out out of order, the same way in every row: the outgoing energies leave a group and come "
+            "back to it, so a bin kept in a register must go back to the row in between")
     return out
+
+
+SAB_REVISIT_PERM = (0, 8, 1, 7, 2, 6, 3, 5, 4)      # of the sorted outgoing energies: low, high, low, high, ...
+
+
+def sab_revisit_table(mode, perm=SAB_REVISIT_PERM):
+    """_sab_small's discrete table with the outgoing energies of every row, and their cosines, taken in
+    the order `perm`: a blend of two rows keeps that order"""
+    t = _sab_small(mode, 2170 + mode)
+    NEi, NEo, NMU = t["NEi"], t["NEo"], t["NMU"]
+    p = np.asarray(perm)
+    t["e_out"] = np.ascontiguousarray(t["e_out"].reshape(NEi, NEo)[:, p]).ravel()
+    t["mu"] = np.ascontiguousarray(t["mu"].reshape(NEi, NEo, NMU)[:, p]).ravel()
+    return t
 
 
 def apply_tol_edge_inputs():

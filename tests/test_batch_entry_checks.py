@@ -57,6 +57,13 @@ def _sab(hip):
     return (p, t, ein, mat), [C.byref(p), C.byref(t), 2, dp(ein), 2, dp(BINS), None, None, dp(mat)], {}
 
 
+def _sab_tab(hip):
+    p = hip.Params.default(4, M)
+    t = hip.SabFlat.from_dict(sab_table(0, 1))
+    ein, mat = np.array([1e-8, 1e-7]), np.zeros(2 * 2 * 8)
+    return (p, t, ein, mat), [C.byref(p), C.byref(t), 8, 2, dp(ein), 2, dp(BINS), None, None, dp(mat), None], {}
+
+
 def _chi(hip):
     c = chi_case()
     nuc, PA, npr, DA, nd, keep = hip.chi_structs(c)
@@ -117,6 +124,7 @@ ENTRIES = {
     "ndpp_law9_tab_batch": lambda hip: _law9(hip, 8),
     "ndpp_elastic_tab_batch": _elastic_tab,
     "ndpp_sab_batch": _sab,
+    "ndpp_sab_tab_batch": _sab_tab,
     "ndpp_chi_batch": _chi,
     "ndpp_convert_distro": _convert,
     "ndpp_expand_moments": _expand,
@@ -154,3 +162,22 @@ def test_batch_entry_refuses_before_the_device(hip, name):
         assert fn(*args) == -5
         assert b"no HIP device" in lib.ndpp_last_error()
     del hold
+
+
+@pytest.mark.parametrize("n_tab", (0, 8))
+def test_sab_entries_refuse_a_bad_cont_ptr_before_the_device(hip, n_tab):
+    """A continuous table whose cont_ptr is missing, or does not start at 0, is an invalid argument for
+    both thermal entry points, device or none."""
+    lib = hip.load()
+    p = hip.Params.default(4, M)
+    t = hip.SabFlat.from_dict(sab_table(2, 1))
+    ein, mat = np.array([1e-8, 1e-7]), np.zeros(2 * 2 * 8)
+    fn = lib.ndpp_sab_tab_batch if n_tab else lib.ndpp_sab_batch
+    args = [C.byref(p), C.byref(t)] + ([n_tab] if n_tab else []) + [2, dp(ein), 2, dp(BINS), None, None, dp(mat)] + \
+        ([None] if n_tab else [])
+    ptr = np.ctypeslib.as_array(t.cont_ptr, shape=(t.n_inelastic_e_in + 1,))
+    ptr[0] = 1
+    assert fn(*args) == -22 and b"cont_ptr[0] must be 0" in lib.ndpp_last_error()
+    ptr[0] = 0
+    t.cont_ptr = None
+    assert fn(*args) == -22 and b"continuous mode without cont_ptr" in lib.ndpp_last_error()

@@ -18,8 +18,8 @@ import pytest
 
 import thermal_tab_ref as tab_ref
 from conftest import OracleParams, dp, load_golden, oracle_params
-from synth import (SAB_EDGE_EXTEND_PTS, SAB_EDGE_TOL, SAB_MODE_SEEDS, apply_tol_edge_inputs, sab_edge_cases,
-                   sab_groups_bins)
+from synth import (SAB_EDGE_EXTEND_PTS, SAB_EDGE_TOL, SAB_G8, SAB_MODE_SEEDS, apply_tol_edge_inputs, sab_edge_cases,
+                   sab_groups_bins, sab_revisit_table)
 
 CASES = sab_edge_cases()
 NAMES = list(CASES)
@@ -30,7 +30,8 @@ VARIANTS = {"orders_1": MODES3, "orders_11": MODES3, "groups_1": MODES3, "groups
             "cont_first_eout_positive": ("",), "cont_edges_on_points": ("",), "cont_two_point_rows": ("",),
             "skewed_min": ("",), "top_inside": MODES3, "bottom_above_zero": MODES3,
             "elastic_edges": ("coherent", "incoherent"), "inel_edges": MODES3, "thresholds_el_below": ("",),
-            "thresholds_el_above": ("",), "exact_with_cosines": ("",), "two_energies": ("",)}
+            "thresholds_el_above": ("",), "exact_with_cosines": ("",), "two_energies": ("",),
+            "eout_revisits_group": ("m0", "m1")}
 
 
 @pytest.fixture(scope="module")
@@ -208,6 +209,40 @@ def _cond_two_energies(name, c):
     assert len(c["ein"]) == 2 and (_p0(name)[1].sum(axis=1) > 0).all()
 
 
+def _group_runs(t, bins, E):
+    """the groups (1-based) the discrete outgoing energies of incoming energy E fall into, in the table's
+    order, consecutive repeats taken once (sab.F90:196-242: the row's bracket, the blend, the group search)"""
+    ei, NEi = t["ei"], t["NEi"]
+    eo = t["e_out"].reshape(NEi, t["NEo"])
+    if E < ei[0]:
+        isab, f = 1, 0.0
+    elif E > t["threshold_inelastic"]:
+        return []
+    elif E == t["threshold_inelastic"]:
+        isab, f = NEi - 1, 1.0
+    else:
+        isab = int(tab_ref.bracket(ei, E))
+        f = (E - ei[isab - 1]) / (ei[isab] - ei[isab - 1])
+    Eout = (1.0 - f) * eo[isab - 1] + f * eo[isab]
+    g = tab_ref.bracket(bins, Eout)[(Eout >= bins[0]) & (Eout < bins[-1])]
+    return [int(v) for k, v in enumerate(g) if k == 0 or v != g[k - 1]]
+
+
+def _cond_eout_revisits(name, c):
+    t, bins, ein = c["table"], c["bins"], c["ein"]
+    assert t["mode"] == _mode_of(name) and t["NEo"] == 9 and np.array_equal(bins, SAB_G8)
+    eo = t["e_out"].reshape(t["NEi"], 9)
+    order = np.argsort(eo, axis=1)
+    assert (order == order[0]).all() and (np.diff(np.sort(eo, axis=1), axis=1) > 0).all()   # one order in every row
+    most = 0
+    for E in ein:
+        runs = _group_runs(t, bins, float(E))
+        assert len(runs) > len(set(runs)), (float(E), runs)              # a group in two separate runs
+        most = max(most, max(runs.count(g) for g in set(runs)))
+    assert most >= 3                                                     # left and come back to at least twice
+    assert len({g for E in ein for g in _group_runs(t, bins, float(E))}) >= 3
+
+
 CONDITIONS = {"orders_1": lambda n, c: _cond_orders(n, c, 1), "orders_11": lambda n, c: _cond_orders(n, c, 11),
               "groups_1": lambda n, c: _cond_groups(n, c, 1), "groups_70": lambda n, c: _cond_groups(n, c, 70),
               "groups_300": lambda n, c: _cond_groups(n, c, 300), "cont_first_eout_positive": _cond_cont_first,
@@ -216,7 +251,8 @@ CONDITIONS = {"orders_1": lambda n, c: _cond_orders(n, c, 1), "orders_11": lambd
               "elastic_edges": _cond_elastic_edges, "inel_edges": _cond_inel_edges,
               "thresholds_el_below": lambda n, c: _cond_thresholds(n, c, True),
               "thresholds_el_above": lambda n, c: _cond_thresholds(n, c, False),
-              "exact_with_cosines": _cond_exact_cosines, "two_energies": _cond_two_energies}
+              "exact_with_cosines": _cond_exact_cosines, "two_energies": _cond_two_energies,
+              "eout_revisits_group": _cond_eout_revisits}
 
 
 def test_case_names_are_the_condition_names():
@@ -248,6 +284,15 @@ def test_case_condition(name):
     if c["cond"].startswith(("groups_", "orders_")):
         assert c["egrid"]
     CONDITIONS[c["cond"]](name, c)
+
+
+@pytest.mark.parametrize("name", ["eout_revisits_group_m0", "eout_revisits_group_m1"])
+def test_eout_revisits_needs_the_permutation(name):
+    """With the outgoing energies back in sorted order the groups are visited once each: the check fails."""
+    c = dict(CASES[name], table=sab_revisit_table(_mode_of(name), perm=range(9)))
+    assert all(len(set(r)) == len(r) for r in (_group_runs(c["table"], c["bins"], float(E)) for E in c["ein"]))
+    with pytest.raises(AssertionError):
+        _cond_eout_revisits(name, c)
 
 
 def test_apply_tol_inputs_hold_the_rows_asked_for():
