@@ -1107,6 +1107,71 @@ void ndpp_nbody_rule(double x[32], double w[32]);
 int ndpp_set_nbody(int enable);
 int ndpp_get_nbody(void);
 
+/* ---- derive a library from a finished one: coarser outgoing groups, cosine
+ * bins from Legendre moments, moments and their enclosure from bins.  Replaces nothing in the
+ * reference.  The arguments are host arrays; rows are independent, so a caller may cut a section into
+ * slices of whole energies without changing a bit.  Every sum below starts from 0.0 and runs
+ * sequentially in ascending index, one IEEE operation per written operator, without contraction in
+ * every build: a host restatement from the tables of ndpp_derive_tables reproduces every output and
+ * every status bit for bit (ndpp_amd/derive.py: groups_numpy, bins_numpy, moments_numpy).
+ *
+ * Status bits of a row (ndpp_derive_bins, ndpp_derive_moments):                                      */
+#define NDPP_DERIVE_NONFINITE 1 /* an input of the row, or an entry of out, is not finite            */
+#define NDPP_DERIVE_NEGBIN 2    /* bins: an output bin is below zero; moments: an input bin is       */
+#define NDPP_DERIVE_ZERO 4      /* bins: a_0 == 0, the row is written as zeros                       */
+/* The tables, host code, no device needed; each is [L][N], 1 <= L <= NDPP_MAX_ORDER,
+ * 1 <= N <= NDPP_MAX_TAB_BINS, anything else (or a NULL pointer) NDPP_EINVAL.
+ *   e_k = -1.0 + (2.0 * k) / N for k < N, e_N = 1.0: the edges of the N equal cosine bins
+ *   P_l(e_k): Bonnet's recurrence upwards in the order of ndpp_scatt_sample,
+ *     P_0 = 1.0, P_1 = x, P_{l+1} = (A_l * x) * P_l - B_l * P_{l-1}, A_l and B_l rounded once
+ *   D_l(x) = P_{l+1}(x) - P_{l-1}(x)
+ *   W[0][k] = (e_{k+1} - e_k) / 2
+ *   W[l][k] = (D_l(e_{k+1}) - D_l(e_k)) / 2, l >= 1: the integral of (l + 1/2) P_l over bin k, a
+ *     difference of the CDF terms ndpp_scatt_sample inverts
+ *   V[0][k] = 1.0;  V[l][k] = (N * W[l][k]) / (2 l + 1), l >= 1: the mean of P_l over bin k
+ *   pmin[l][k], pmax[l][k]: the smallest and the largest of P_l at the two edges of bin k and at the
+ *     roots of P_l' strictly inside it, moved outward by 8 * DBL_EPSILON (8 ulp of 1) so that the
+ *     evaluation error of P_l cannot make a bound too tight.  The roots are found on the host by
+ *     bisection between neighbouring roots of P_l, down to neighbouring doubles.                     */
+int ndpp_derive_tables(int L, int N, double *W /* [L][N] */, double *V, double *pmin, double *pmax);
+/* Segmented sum over the middle axis.  first[Gc + 1] strictly increasing, first[0] = 0, first[Gc] = G:
+ *   out[e][c][l] = mat[e][first[c]][l] + ... + mat[e][first[c+1] - 1][l]
+ * Serves outgoing groups (any L >= 1: moments or bins alike), chi rows (L = 1) and, on the view
+ * [n * G][N][1] of a tabular section, the merging of N bins into Gc = N' bins, N' a divisor of N.
+ * NDPP_EINVAL, decided before the device is touched: n < 0, G < 1, L < 1, Gc outside 1..G, first NULL
+ * or not as above, for n > 0 a NULL array, a G * L that does not fit an index, sizes whose bytes
+ * overflow.  Without a device NDPP_EDEVICE; with one, n == 0 is an empty success.                    */
+int ndpp_derive_groups(long n, int G, int L, const double *mat /* [n][G][L] */, int Gc,
+                       const int *first /* [Gc+1] */, double *out /* [n][Gc][L] */);
+/* Bins from moments.  With r = (e, g) a row of L moments a_l = mat[r][l]:
+ *   t_k = sum over l of a_l * W[l][k]          (multiply, then add)
+ *   a_0 == 0: NDPP_DERIVE_ZERO and t_k = 0.0 for every k, whatever the other moments hold (the
+ *     writers drop such a row; a NaN or infinite a_l of it still sets NDPP_DERIVE_NONFINITE)
+ *   out[r][k] = t_k;  NDPP_DERIVE_NONFINITE: an a_l or a t_k is not finite;  NDPP_DERIVE_NEGBIN: a
+ *   t_k < 0 -- the row's density is negative somewhere and wants --repair-positivity
+ *   (ndpp_scatt_repair) first; the bins are written as they come out.
+ * sum_k t_k equals a_0 to rounding.  NDPP_EINVAL before the device is touched: n < 0, G < 1, L outside
+ * 1..NDPP_MAX_ORDER, N outside 1..NDPP_MAX_TAB_BINS, for n > 0 a NULL array, an index or a size that
+ * does not fit.  Without a device NDPP_EDEVICE; with one, n == 0 is an empty success.                */
+int ndpp_derive_bins(long n, int G, int L, const double *mat /* [n][G][L] */, int N,
+                     double *out /* [n][G][N] */, int *status /* [n][G] */);
+/* Moments from bins.  With r = (e, g) a row of N bin integrals t_k = mat[r][k]:
+ *   out[r][l] = sum over k of t_k * V[l][k]: the moments of the histogram t_k / (e_{k+1} - e_k);
+ *     out[r][0] is the row's mass S exactly as ndpp_scatt_sample sums it
+ *   lo[r][l]  = sum over k of t_k * pmin[l][k],  hi[r][l] = sum over k of t_k * pmax[l][k]
+ *   NDPP_DERIVE_NEGBIN: a t_k < 0;  NDPP_DERIVE_NONFINITE: a t_k or an out[r][l] is not finite
+ * lo and hi may be NULL (either or both).  For a row without NDPP_DERIVE_NEGBIN and ANY non-negative
+ * density with these bin integrals, its moment a_l satisfies
+ *   lo[r][l] - 1e-13 * S <= a_l <= hi[r][l] + 1e-13 * S
+ * (the 1e-13 covers the rounding of the sums), and lo <= out <= hi holds as computed.  The histogram's
+ * own moments are one member of that family, not the moments of the density the bins came from
+ * (DESIGN.md section 21 has the distances).  For a row with NDPP_DERIVE_NEGBIN lo and hi mean
+ * nothing: they are written, and enclose nothing.
+ * NDPP_EINVAL and NDPP_EDEVICE as ndpp_derive_bins (out and status may not be NULL).                 */
+int ndpp_derive_moments(long n, int G, int N, const double *mat /* [n][G][N] */, int L,
+                        double *out /* [n][G][L] */, double *lo, double *hi /* [n][G][L], may be NULL */,
+                        int *status /* [n][G] */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -28,7 +28,7 @@ SOURCES = [(CSRC / "ndpp_hip.hip", False), (CSRC / "fg_strict_stages.hip", True)
            (CSRC / "thin_kernels.hip", True), (CSRC / "compare_kernels.hip", True),
            (CSRC / "minimum_kernels.hip", True), (CSRC / "repair_kernels.hip", True),
            (CSRC / "sample_kernels.hip", True), (CSRC / "score_kernels.hip", True),
-           (CSRC / "nbody_kernels.hip", True)]
+           (CSRC / "nbody_kernels.hip", True), (CSRC / "derive_kernels.hip", True)]
 HEADERS = [CSRC / "ndpp_math.h", CSRC / "fg_pipeline.h", CSRC / "fg_device.h", CSRC / "kernels.h", CSRC / "dev_util.h",
            CSRC / "file4_device.h", CSRC / "file6_device.h", CSRC / "section_util.h", CSRC / "minimum_row.h",
            CSRC / "legendre_int.h", CSRC / "legendre_ref_forms.h", CSRC / "exp_tab.inc", CSRC / "nbody_rule.h",

@@ -33,6 +33,8 @@ SAMPLE_OK, SAMPLE_SKIPPED, SAMPLE_BADROW, SAMPLE_ZEROROW, SAMPLE_NEGDENSITY = 0,
 # per-event status of ndpp_scatt_score, its chunk length, and the names of ndpp_scatt_score_info's figures
 SCORE_OK, SCORE_SKIPPED, SCORE_BADROW, SCORE_ZEROROW = 0, 1, 2, 3
 NDPP_SCORE_CHUNK = 256
+# per-row status bits of ndpp_derive_bins and ndpp_derive_moments
+DERIVE_NONFINITE, DERIVE_NEGBIN, DERIVE_ZERO = 1, 2, 4
 SCORE_INFO = ["bracket_ms", "factor_ms", "group_ms", "upload_ms", "kernel_ms", "download_ms", "passes", "scored",
               "chunks"]
 
@@ -58,6 +60,7 @@ EXPORTS = [
     "ndpp_scatt_minimum", "ndpp_scatt_minimum_evals", "ndpp_scatt_repair", "ndpp_scatt_repair_evals",
     "ndpp_scatt_sample", "ndpp_sample_brackets", "ndpp_scatt_score", "ndpp_scatt_score_info",
     "ndpp_nbody_leg_batch", "ndpp_nbody_rule", "ndpp_set_nbody", "ndpp_get_nbody",
+    "ndpp_derive_tables", "ndpp_derive_groups", "ndpp_derive_bins", "ndpp_derive_moments",
 ]
 
 
@@ -662,6 +665,11 @@ def load(build_if_missing: bool = False, torch_compat: bool | None = None) -> C.
         lib.ndpp_set_nbody.argtypes = [C.c_int]
         lib.ndpp_set_nbody.restype = C.c_int
         lib.ndpp_get_nbody.restype = C.c_int
+        lib.ndpp_derive_tables.argtypes = [C.c_int, C.c_int] + [c_double_p] * 4
+        lib.ndpp_derive_groups.argtypes = [C.c_long, C.c_int, C.c_int, c_double_p, C.c_int, c_int_p, c_double_p]
+        lib.ndpp_derive_bins.argtypes = [C.c_long, C.c_int, C.c_int, c_double_p, C.c_int, c_double_p, c_int_p]
+        lib.ndpp_derive_moments.argtypes = [C.c_long, C.c_int, C.c_int, c_double_p, C.c_int, c_double_p, c_double_p,
+                                            c_double_p, c_int_p]
     _lib = lib
     return lib
 
@@ -1159,6 +1167,55 @@ def scatt_score_info() -> dict:
     out = np.zeros(len(SCORE_INFO))
     _check(load().ndpp_scatt_score_info(_dp(out), len(out)))
     return dict(zip(SCORE_INFO, (float(v) for v in out)))
+
+
+def derive_tables(L: int, N: int):
+    """ndpp_derive_tables: (W, V, pmin, pmax), each [L][N] -- the bin integrals of (l + 1/2) P_l, the bin
+    means of P_l and the extremes of P_l on the N equal cosine bins (include/ndpp_hip.h).  Host code."""
+    L, N = int(L), int(N)
+    shape = (max(L, 1), max(N, 1))
+    W, V, pmin, pmax = (np.zeros(shape) for _ in range(4))
+    _check(load().ndpp_derive_tables(L, N, _dp(W), _dp(V), _dp(pmin), _dp(pmax)))
+    return W, V, pmin, pmax
+
+
+def _derive_rows(mat):
+    mat = _f64(mat)
+    if mat.ndim != 3:
+        raise ValueError(f"mat must be (n, G, L), got {mat.shape}")
+    return mat
+
+
+def derive_groups(mat, first) -> np.ndarray:
+    """ndpp_derive_groups: out[e][c][l] = the sum of mat[e][g][l] over first[c] <= g < first[c+1]."""
+    mat, first = _derive_rows(mat), _i32(first).ravel()
+    n, G, L = mat.shape
+    Gc = len(first) - 1
+    out = np.zeros((n, max(Gc, 0), L))
+    _check(load().ndpp_derive_groups(n, G, L, _dp(mat), Gc, _ip(first), _dp(out)))
+    return out
+
+
+def derive_bins(mat, N: int):
+    """ndpp_derive_bins: (bins[n][G][N], status[n][G] int32) of the Legendre rows mat[n][G][L]."""
+    mat, N = _derive_rows(mat), int(N)
+    n, G, L = mat.shape
+    out, status = np.zeros((n, G, max(N, 0))), np.zeros((n, G), dtype=np.int32)
+    _check(load().ndpp_derive_bins(n, G, L, _dp(mat), N, _dp(out), _ip(status)))
+    return out, status
+
+
+def derive_moments(mat, L: int, bounds: bool = True):
+    """ndpp_derive_moments: (moments, lo, hi, status) of the tabular rows mat[n][G][N], each [n][G][L]
+    (lo and hi None with bounds=False) and status[n][G] int32."""
+    mat, L = _derive_rows(mat), int(L)
+    n, G, N = mat.shape
+    shape = (n, G, max(L, 0))
+    out, status = np.zeros(shape), np.zeros((n, G), dtype=np.int32)
+    lo, hi = (np.zeros(shape), np.zeros(shape)) if bounds else (None, None)
+    _check(load().ndpp_derive_moments(n, G, N, _dp(mat), L, _dp(out), _dp(lo) if bounds else None,
+                                      _dp(hi) if bounds else None, _ip(status)))
+    return out, lo, hi, status
 
 
 def _thin_args(x, y, y2, tokeep):
