@@ -1102,10 +1102,74 @@ void ndpp_nbody_rule(double x[32], double w[32]);
  * ScattData of its own: no angular distribution is fabricated for it, its grid is
  * {max(threshold energy, e_bins[0]), top edge} (none when that is not below the top edge), and its
  * rows come from ndpp_nbody_leg_batch, scaled and summed like any other reaction's.  A tabular call
- * that meets such a reaction returns NDPP_EINVAL: law 66 has Legendre output only.  With 0 nothing
- * changes anywhere.  ndpp_scattdata_shape and ndpp_convert_distro do not read it.                   */
+ * that meets such a reaction returns NDPP_EINVAL ("law 66 has Legendre output only") unless
+ * ndpp_set_nbody_tab is on as well (below).  With 0 nothing changes anywhere.  ndpp_scattdata_shape
+ * and ndpp_convert_distro do not read it.                                                           */
 int ndpp_set_nbody(int enable);
 int ndpp_get_nbody(void);
+
+/* ---- ACE law 66 in cosine bins ("Tabular output") ---------------------------
+ * The tabular counterpart of ndpp_nbody_leg_batch: the P0 of a group split into n_tab = N equal bins of
+ * the lab cosine, 1 <= N <= NDPP_MAX_TAB_BINS, with the edges of the other tabular calls
+ * (b_k = -1 + (2 * k) / N, b_N = 1).
+ *   out[e][g][k]: bin k of group [lo, hi] at E = ein[e], fully written, not scaled; never negative
+ *   status[e]: as ndpp_nbody_leg_batch.  May be NULL.
+ * The symbols are those of ndpp_nbody_leg_batch: A, Q, n, Ap, Emax, E0, rE0 = sqrt(E0), rEm =
+ * sqrt(Emax), wl, wh, K = 2 / B, x[j], w[j]; p = 3n/2 - 3 (1.5, 3, 4.5).  In the lab variables
+ * (s' = sqrt(E'), mu) the CM energy is T(m, s') = (s' * s' + E0) - 2 m s' rE0, the density is
+ * proportional to s' * s' * y^(p-1) with y(m, s') = 1 - T / Emax where that is positive, and its
+ * integral over the cosine from m0 to m1 at fixed s' is
+ *   C * s' * (max(y(m1, s'), 0)^p - max(y(m0, s'), 0)^p),   C = K / (4 p rEm rE0):
+ * a bin is a one-dimensional integral over s' and nothing else.  The difference of the two powers is
+ * never formed: it is the product d * D below, each factor without cancellation, so a bin cannot come
+ * out negative and a heavy target (E0 << Emax) loses no digits.
+ * A row with an E that is not positive and finite (NDPP_ST_RANGE), or with Emax <= 0, is zero; so is
+ * a group with hi <= wl * wl or lo >= wh * wh (the test of ndpp_nbody_leg_batch), without integrating.
+ * Otherwise, in IEEE double, one operation per written operator, no contraction:
+ *   rlo = sqrt(lo), rhi = sqrt(hi), a = max(rlo, wl), b = min(rhi, wh)   (x > y ? x : y, x < y ? x : y)
+ *   m0 = b_k, m1 = b_(k+1), dm = m1 - m0
+ *   for m in (m0, m1): c = m * rE0, disc = Emax - E0 * ((1 - m) * (1 + m)): Emax y(m, s') is
+ *     disc - (s' - c)^2, and y is evaluated in this form (c0, disc0 and c1, disc1 below).  Just above
+ *     the threshold Emax << E0, and 1 - T / Emax as written would lose log10(E0 / Emax) digits.
+ *   breakpoints: for m in (m0, m1), when disc > 0: the two roots c - sqrt(disc), c + sqrt(disc) of
+ *     y(m, s') = 0, each kept when a < root < b.  a, b and the kept roots, sorted, equal values once:
+ *     consecutive values pa < pb are the pieces, at most five, ascending.  (b <= a: no piece.)
+ *   node j of a piece, len = pb - pa:
+ *     u = 0.5 + 0.5 * x[j], h = (u * u) * (3 - 2 * u), sp = pa + len * h
+ *     wgt = ((0.5 * w[j]) * len) * ((6 * u) * (1 - u))
+ *     (s' = pa + len h(u): at a root the integrand starts like (s' - root)^p, p = 3/2 for n = 3; in u
+ *     it is smooth at both ends of the piece)
+ *     t0 = sp - c0, t1 = sp - c1
+ *     y0 = (disc0 - t0 * t0) / Emax,  y1 = (disc1 - t1 * t1) / Emax
+ *     y0c = y0 > 0 ? y0 : 0,  y1c = y1 > 0 ? y1 : 0
+ *     f = 0.0 unless y1c > 0; then
+ *       d = (((2 * sp) * rE0) * dm) / Emax where y0 > 0 (this is y1 - y0 without the subtraction),
+ *           y1c otherwise
+ *       q2 = (y1c * y1c + y1c * y0c) + y0c * y0c
+ *       D = (y1c^p - y0c^p) / (y1c - y0c), as
+ *         n = 4: q2
+ *         n = 3: q2 / (y1c * sqrt(y1c) + y0c * sqrt(y0c))
+ *         n = 5: a3 = (y1c * y1c) * y1c, b3 = (y0c * y0c) * y0c,
+ *                (q2 * ((a3 * a3 + a3 * b3) + b3 * b3)) / ((a3 * y1c) * sqrt(y1c) + (b3 * y0c) * sqrt(y0c))
+ *       f = (sp * d) * D
+ *     piece = piece + wgt * f, from 0.0, j ascending
+ *   total = the pieces, from 0.0, ascending;  out[e][g][k] = (K / (((4 * p) * rEm) * rE0)) * total.
+ * tests/nbody_tab_ref.py restates the operations (nbody_tab_numpy gives the same bits) and measures
+ * the rule against a 96-point one, against the Legendre call's P0 and against an independent route
+ * through the CM variables; the figures, and the known limit E0 << Emax for n = 3 (a very heavy target:
+ * 7.5e-10 at A = 1e6 and N = 1), are in profiles/nbody_tab/README.md.
+ * NDPP_EINVAL, decided before the device is touched: n_tab outside 1..NDPP_MAX_TAB_BINS, and the
+ * argument checks of ndpp_nbody_leg_batch except the order, which tabular output does not read.
+ * n_ein == 0 is an empty success.  Without a device NDPP_EDEVICE.                                    */
+int ndpp_nbody_tab_batch(const ndpp_params *p, int n_tab, double awr, double Q, int n_bodies,
+                         double Ap, int n_ein, const double *ein, int G, const double *e_bins,
+                         double *out /* [n_ein][G][n_tab] */, int *status /* [n_ein] */);
+/* Opt-in, process-wide, default 0; returns the previous value.  Read once per nuclide, next to
+ * ndpp_get_nbody, and acts only when that is 1 as well: a tabular whole-nuclide call then initialises
+ * a law-66 reaction as a Legendre call does and takes its rows from ndpp_nbody_tab_batch.  With 0 the
+ * tabular call refuses as before.                                                                    */
+int ndpp_set_nbody_tab(int enable);
+int ndpp_get_nbody_tab(void);
 
 /* ---- derive a library from a finished one: coarser outgoing groups, cosine
  * bins from Legendre moments, moments and their enclosure from bins.  Replaces nothing in the

@@ -23,6 +23,7 @@ from .lib import (_check, Params, Stats, NdppError, load, library_path, mu_grid,
                   scatt_sample, sample_brackets, SAMPLE_OK, SAMPLE_SKIPPED, SAMPLE_BADROW, SAMPLE_ZEROROW, SAMPLE_NEGDENSITY,
                   scatt_score, scatt_score_info, SCORE_OK, SCORE_SKIPPED, SCORE_BADROW, SCORE_ZEROROW,
                   nbody_leg_batch, nbody_rule, set_nbody, get_nbody,
+                  nbody_tab_batch, set_nbody_tab, get_nbody_tab,
                   derive_tables, derive_groups, derive_bins, derive_moments, DERIVE_NONFINITE, DERIVE_NEGBIN,
                   DERIVE_ZERO, NDPP_EINVAL, NDPP_EDEVICE)
 from .scatt import binary_search, elastic_brackets, calc_elastic_grid  # noqa: F401

@@ -149,6 +149,10 @@ int law9_batch_sink(const ndpp_params* p, int n_ein, const double* ein, const in
 int nbody_batch_sink(const ndpp_params* p, double awr, double Q, int n_bodies, double Ap, int n_ein,
                      const double* ein, int G, const double* e_bins, double* out, int* status,
                      DeviceSink* sink);
+// nbody_kernels.hip: ndpp_nbody_tab_batch with a sink (n_tab bins per group)
+int nbody_tab_batch_sink(const ndpp_params* p, int n_tab, double awr, double Q, int n_bodies, double Ap, int n_ein,
+                         const double* ein, int G, const double* e_bins, double* out, int* status,
+                         DeviceSink* sink);
 // tab_kernels.hip: law9_batch_sink's integrating kernel for n_tab = N > 0 (raw [n_ein][2][G][N], null
 // stream), and the tabular counterpart of elastic_leg_batch_sink
 void launch_law9_tab(int n_ein, const double* ein, const int* row_lo, int mu_bins, const double* f_tab,

@@ -258,6 +258,7 @@ struct Call {
   const double* e_bins;
   int n_tab, G, L, M;     // n_tab = 0: L = p->order Legendre moments; n_tab > 0: L = n_tab bins
   bool nbody;             // ndpp_set_nbody, read once per call: law 66 is integrated
+  bool nbody_tab;         // ndpp_set_nbody_tab, read with it: law 66 also in a tabular call (acts only with nbody)
   size_t GL;
   double Etop;
   Hooks hooks;
@@ -265,7 +266,8 @@ struct Call {
   Call(const ndpp_params* p_, const ndpp_ace_nuclide* nuc_, int n_bins_, const double* e_bins_, int n_tab_)
       : p(p_), nuc(nuc_), n_bins(n_bins_), e_bins(e_bins_), n_tab(n_tab_), G(n_bins_ - 1),
         L(n_tab_ > 0 ? n_tab_ : p_->order), M(p_->mu_bins), GL((size_t)G * L), Etop(e_bins_[G]),
-        nbody(ndpp_get_nbody() != 0), hooks(read_hooks()), hc(hooks.host_timing) {}
+        nbody(ndpp_get_nbody() != 0), nbody_tab(ndpp_get_nbody_tab() != 0), hooks(read_hooks()),
+        hc(hooks.host_timing) {}
 };
 
 // ---- init + convert_distro for every reaction and nested distribution (:59-106)
@@ -387,7 +389,7 @@ int convert_reactions(const Call& c, std::vector<SD>* sds) {
       sd.rxn = &rx;
       sd.is_init = is_init != 0;
       if (c.nbody && ed && ed->law == 66 && valid_scatter(rx.MT)) {
-        if (c.n_tab > 0)
+        if (c.n_tab > 0 && !c.nbody_tab)
           return fail(NDPP_EINVAL, "MT %d: law 66 (N-body phase space) has Legendre output only", rx.MT);
         if (ed->n_data < 2 || !ed->data)
           return fail(NDPP_EINVAL, "MT %d: law 66 needs its 2 data words (the number of bodies and Ap)", rx.MT);
@@ -548,6 +550,9 @@ int integrate_reaction(const Call& c, const SD& sd, int kind, double cutoff, con
                        DeviceSink* sink) {
   const ndpp_ace_nuclide* nuc = c.nuc;
   std::vector<int> status(s.nb);
+  if (kind == 5 && c.n_tab > 0)
+    return nbody_tab_batch_sink(c.p, c.n_tab, nuc->awr, sd.rxn->Q_value, (int)sd.edist->data[0], sd.edist->data[1],
+                                s.nb, s.ein.data(), c.G, c.e_bins, res, status.data(), sink);
   if (kind == 5)
     return nbody_batch_sink(c.p, nuc->awr, sd.rxn->Q_value, (int)sd.edist->data[0], sd.edist->data[1], s.nb,
                             s.ein.data(), c.G, c.e_bins, res, status.data(), sink);

@@ -60,6 +60,7 @@ EXPORTS = [
     "ndpp_scatt_minimum", "ndpp_scatt_minimum_evals", "ndpp_scatt_repair", "ndpp_scatt_repair_evals",
     "ndpp_scatt_sample", "ndpp_sample_brackets", "ndpp_scatt_score", "ndpp_scatt_score_info",
     "ndpp_nbody_leg_batch", "ndpp_nbody_rule", "ndpp_set_nbody", "ndpp_get_nbody",
+    "ndpp_nbody_tab_batch", "ndpp_set_nbody_tab", "ndpp_get_nbody_tab",
     "ndpp_derive_tables", "ndpp_derive_groups", "ndpp_derive_bins", "ndpp_derive_moments",
 ]
 
@@ -665,6 +666,11 @@ def load(build_if_missing: bool = False, torch_compat: bool | None = None) -> C.
         lib.ndpp_set_nbody.argtypes = [C.c_int]
         lib.ndpp_set_nbody.restype = C.c_int
         lib.ndpp_get_nbody.restype = C.c_int
+        lib.ndpp_nbody_tab_batch.argtypes = [PP, C.c_int, C.c_double, C.c_double, C.c_int, C.c_double, C.c_int,
+                                             c_double_p, C.c_int, c_double_p, c_double_p, c_int_p]
+        lib.ndpp_set_nbody_tab.argtypes = [C.c_int]
+        lib.ndpp_set_nbody_tab.restype = C.c_int
+        lib.ndpp_get_nbody_tab.restype = C.c_int
         lib.ndpp_derive_tables.argtypes = [C.c_int, C.c_int] + [c_double_p] * 4
         lib.ndpp_derive_groups.argtypes = [C.c_long, C.c_int, C.c_int, c_double_p, C.c_int, c_int_p, c_double_p]
         lib.ndpp_derive_bins.argtypes = [C.c_long, C.c_int, C.c_int, c_double_p, C.c_int, c_double_p, c_int_p]
@@ -880,6 +886,27 @@ def set_nbody(enable: bool) -> bool:
 
 def get_nbody() -> bool:
     return bool(load().ndpp_get_nbody())
+
+
+def nbody_tab_batch(params: Params, n_tab, awr, Q, n_bodies, Ap, ein, e_bins):
+    """ndpp_nbody_tab_batch: nbody_leg_batch's P0 in n_tab lab-cosine bins.  Returns
+    out[n_ein][G][n_tab], status[n_ein]."""
+    ein, e_bins = _f64(ein), _f64(e_bins)
+    G = e_bins.shape[0] - 1
+    p, out, status = _batch_out(params, params.mu_bins, len(ein), G, n_tab)
+    _check(load().ndpp_nbody_tab_batch(C.byref(p), int(n_tab), float(awr), float(Q), int(n_bodies), float(Ap),
+                                       len(ein), _dp(ein), G, _dp(e_bins), _dp(out), _ip(status)))
+    return out, status
+
+
+def set_nbody_tab(enable: bool) -> bool:
+    """ndpp_set_nbody_tab: whether a tabular whole-nuclide call integrates law 66 too (process-wide,
+    default off; acts only with set_nbody on).  Returns the previous setting."""
+    return bool(load().ndpp_set_nbody_tab(int(bool(enable))))
+
+
+def get_nbody_tab() -> bool:
+    return bool(load().ndpp_get_nbody_tab())
 
 
 SCATT_LEGENDRE, SCATT_TABULAR, MAX_TAB_BINS = 0, 1, 128

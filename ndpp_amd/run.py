@@ -73,13 +73,17 @@ Positivity (ndpp_amd.repair; Legendre output only):
   --repair-undecided   also repair rows whose minimum is within the tolerance of zero
                        Each of the four is an input error without --repair-positivity.
 
-N-body phase space (ACE law 66; Legendre output only):
+N-body phase space (ACE law 66):
   --nbody              integrate the reactions whose energy distribution is law 66 (deuterium's
                        (n,2n) is the best-known one) in closed form (lib.set_nbody; DESIGN.md section
                        20).  Without the flag they add nothing to the library, as in the reference.
                        The option is set for the run's library calls and put back afterwards; how many
                        reactions were integrated under law 66 goes under "nbody" in --json.  A tabular
-                       run whose tables carry law 66 is an input error."""
+                       run whose tables carry law 66 is an input error.
+  --nbody-tabular      --nbody, and in a tabular run law 66 goes into the bins too (lib.set_nbody_tab:
+                       ndpp_nbody_tab_batch, bins that cannot go negative) instead of being an input
+                       error.  Both options are set for the run and put back afterwards; "nbody" in
+                       --json gains "tabular": true."""
 from __future__ import annotations
 
 import argparse
@@ -494,8 +498,10 @@ def write_library(run_dir, files: list, xml: bytes) -> list:
 
 
 def run(run_dir, json_path=None, out=sys.stdout, grid_opts: dict | None = None,
-        repair_opts: dict | None = None, thermal_tabular: bool = False, nbody: bool = False) -> int:
+        repair_opts: dict | None = None, thermal_tabular: bool = False, nbody: bool = False,
+        nbody_tabular: bool = False) -> int:
     """The whole driver; returns the exit status."""
+    nbody = nbody or nbody_tabular                          # --nbody-tabular implies --nbody
     run_dir = Path(run_dir)
     t_start = time.perf_counter()
     try:
@@ -516,9 +522,9 @@ def run(run_dir, json_path=None, out=sys.stdout, grid_opts: dict | None = None,
         if not tables:
             raise InputError("no neutron or thermal tables to process")
         law66 = nbody_reactions(tables, s["energy_bins"]) if nbody else {}
-        if law66 and s["scatt_type"] == "tabular":
+        if law66 and s["scatt_type"] == "tabular" and not nbody_tabular:
             raise InputError(f"--nbody: {', '.join(law66)} carries ACE law 66, which has Legendre output only: give "
-                             "it with <scatt_type> legendre")
+                             "it with <scatt_type> legendre, or give --nbody-tabular")
     except InputError as e:
         print(f"ndpp_amd.run: input error: {e}", file=sys.stderr)
         return EXIT_INPUT
@@ -532,12 +538,15 @@ def run(run_dir, json_path=None, out=sys.stdout, grid_opts: dict | None = None,
             return EXIT_INPUT
         repair_rep = None
         nbody_before = lib.set_nbody(True) if nbody else False
+        nbody_tab_before = lib.set_nbody_tab(True) if nbody_tabular else False
         try:
             if repair_opts is not None:
                 files, recs, grid_rep, repair_rep = compute(s, tables, grid_opts, repair_opts)
             else:
                 files, recs, grid_rep = compute(s, tables, grid_opts)
         finally:
+            if nbody_tabular:
+                lib.set_nbody_tab(nbody_tab_before)
             if nbody:
                 lib.set_nbody(nbody_before)
         xml = lib_xml_of(s, run_dir, tables)
@@ -576,6 +585,8 @@ def run(run_dir, json_path=None, out=sys.stdout, grid_opts: dict | None = None,
             rec["grid"] = grid_rep
         if nbody:
             rec["nbody"] = dict(reactions=sum(law66.values()), tables=law66)
+            if nbody_tabular:
+                rec["nbody"]["tabular"] = True
         if repair_rep is not None:
             rec["repair"] = dict(repair_opts, tables=[dict(name=t["name"], kind=t["kind"], **t["report"].as_dict())
                                                       for t in repair_rep])
@@ -670,6 +681,9 @@ def main(argv=None) -> int:
     ap.add_argument("--nbody", action="store_true",
                     help="integrate the reactions under ACE law 66 (N-body phase space) in closed form; without it "
                          "they add nothing, as in the reference (Legendre output only)")
+    ap.add_argument("--nbody-tabular", action="store_true",
+                    help="--nbody, and with scatt_type tabular the law-66 reactions go into the bins too (without "
+                         "it such a run is refused)")
     a = ap.parse_args(argv)
     try:
         grid_opts = _grid_options(a)
@@ -678,7 +692,7 @@ def main(argv=None) -> int:
         print(f"ndpp_amd.run: input error: {e}", file=sys.stderr)
         return EXIT_INPUT
     return run(a.run_dir, a.json, grid_opts=grid_opts, repair_opts=repair_opts, thermal_tabular=a.thermal_tabular,
-               nbody=a.nbody)
+               nbody=a.nbody, nbody_tabular=a.nbody_tabular)
 
 
 if __name__ == "__main__":

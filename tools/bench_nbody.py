@@ -11,6 +11,11 @@ Per case, warm (one untimed call of the same shape first), --repeat timed calls 
   items       (energy, group) pairs; live: those whose group meets the lab window, which integrate
   nodes       inner-rule evaluations of the live items: 32 x 32 per piece
   row_sum     the worst |sum over the groups of P0 - 1|: the edges cover the window
+Then the tabular call (ndpp_nbody_tab_batch) next to the Legendre one, on the same 1000 energies x 70
+groups: P5 (L = 6), N = 32 and N = 128 bins, one warm call each and then --repeat rounds that alternate
+the three (leg, tab32, tab128, leg, ...), so that a drift of the clocks meets all three alike.  Per
+call kernel_ms and call_s as above; row_sum is the worst |sum over groups and bins - 1|, min_bin the
+smallest bin (never negative), sum_rule the worst |sum of the bins - P0 of the Legendre call|.
 No GPU: it fails, it does not fall back.
 
     python tools/bench_nbody.py [--repeat 3] [--out FILE]
@@ -43,6 +48,41 @@ def work(ein, bins):
         Tb = (np.sqrt(edge) + sign * rE0) ** 2
         pieces += (Tb > 0.0) & (Tb < Emax[:, None])
     return int(live.sum()), int(pieces[live].sum())                  # (duplicates counted: an upper bound)
+
+
+def tabular(ndpp_amd, lib, thr, repeat) -> list:
+    """the tabular call at N = 32 and 128 next to the Legendre call at P5: alternating rounds"""
+    n_ein, bins = 1000, np.concatenate([[0.0], np.geomspace(1e-11, 20.0, 70)])
+    ein = np.linspace(thr * 1.001, 20.0, n_ein)
+    p = ndpp_amd.Params.default(6, 65)
+    calls = [("leg_P5", lambda: ndpp_amd.nbody_leg_batch(p, AWR, Q, N_BODIES, AP, ein, bins)),
+             ("tab_N32", lambda: ndpp_amd.nbody_tab_batch(p, 32, AWR, Q, N_BODIES, AP, ein, bins)),
+             ("tab_N128", lambda: ndpp_amd.nbody_tab_batch(p, 128, AWR, Q, N_BODIES, AP, ein, bins))]
+    out, call_s, kernel_ms = {}, {k: [] for k, _ in calls}, {k: [] for k, _ in calls}
+    for _, f in calls:
+        f()                                                             # warm: this shape, untimed
+    for _ in range(repeat):
+        for name, f in calls:
+            t0 = time.perf_counter()
+            out[name], st = f()
+            call_s[name].append(time.perf_counter() - t0)
+            kernel_ms[name].append(float(lib.ndpp_last_gpu_ms()))
+            assert not st.any()
+    p0 = out["leg_P5"][:, :, 0]
+    lines = []
+    for name, _ in calls:
+        o = out[name]
+        rec = dict(case=name, n_ein=n_ein, G=len(bins) - 1, L=o.shape[2], elements=int(o.size),
+                   kernel_ms=round(min(kernel_ms[name]), 3), kernel_ms_all=[round(v, 3) for v in kernel_ms[name]],
+                   call_s=round(min(call_s[name]), 5), call_s_all=[round(v, 5) for v in call_s[name]])
+        if name == "leg_P5":
+            rec["row_sum"] = float(np.abs(p0.sum(axis=1) - 1.0).max())
+        else:
+            rec.update(row_sum=float(np.abs(o.sum(axis=(1, 2)) - 1.0).max()), min_bin=float(o.min()),
+                       sum_rule=float(np.abs(o.sum(axis=2) - p0).max()))
+        lines.append(rec)
+        print(json.dumps(rec), flush=True)
+    return lines
 
 
 def main(argv=None) -> int:
@@ -78,6 +118,7 @@ def main(argv=None) -> int:
         rec["nodes_per_s"] = round(rec["nodes"] / (rec["kernel_ms"] * 1e-3)) if rec["kernel_ms"] > 0 else None
         lines.append(rec)
         print(json.dumps(rec), flush=True)
+    lines += tabular(ndpp_amd, lib, thr, a.repeat)
     if a.out:
         Path(a.out).parent.mkdir(parents=True, exist_ok=True)
         Path(a.out).write_text("".join(json.dumps(r) + "\n" for r in lines))
